@@ -33,6 +33,13 @@ ranks with an RCCL all-reduce of the reduced camera system per LM trial (SURVEY.
 Workloads: `--workload c3` (default, BASELINE configs[2]), `c4` (configs[3]'s per-GPU sequence:
 OIVIO-shaped 640x512 stereo, 600 keypoints, SG N=600; with --gpus 8 one sequence per GPU) or `c5`
 (configs[4]: synthetic 1920x1080 stereo, 2048 keypoints, SG N=2048, 30-keyframe / 10k-landmark BA).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: set-up, W warmup
+steps, the N timed steps, one JSON line (with the stage times the timed region's own HIP events give).  `--full`
+adds what takes runs of its own: the same steps at the other precision, the instrumented BA pass (the BA rows
+of stages_roofline), the CPU baseline and the trajectory ATE.  `--dump-outputs DIR` writes the last timed
+step's results (the arrays a caller of the pipeline receives) as DIR/<name>.npy; the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import gc
@@ -369,11 +376,23 @@ def main():
                     help="1: the BA runs only on the reserved CUs (disjoint from SP/SG)")
     ap.add_argument("--skip", default="", help="diagnostics only: comma list of stages to leave out (sp,sg,ba)")
     ap.add_argument("--ba-ktime-steps", type=int, default=20,
-                    help="steps of the instrumented pass after the timed region whose BA calls time the BA's two "
+                    help="with --full: steps of the instrumented pass after the timed region whose BA calls time the BA's two "
                          "per-trial launches with HIP events (0: off); the timed region carries no BA events")
     ap.add_argument("--single-precision", action="store_true",
                     help="skip the second (other-precision) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline run: the other-precision measurement, the instrumented BA pass (BA "
+                         "roofline rows), the CPU baseline and the trajectory ATE (each can still be switched off "
+                         "with its own option); a plain run only sets up, warms up, times --steps steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (SuperPoint features, "
+                         "SuperGlue matches, lines and their stereo association, the local BA's result) as "
+                         "DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.skip:
+        ap.error("--dump-outputs needs the whole step (no --skip)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -396,7 +415,8 @@ def main():
     # the second measurement of the same run: the fp16 headline is paired with the split-fp16 SuperPoint (the
     # fp32 path's keypoint sets, profiles/r06_c1_plumbing.json), the others with fp16
     other_prec = {"fp16": "fp16x3", "fp16x3": "fp16", "fp32": "fp16"}
-    precs = [args.precision] + ([other_prec[args.precision]] if world == 1 and not args.single_precision else [])
+    precs = [args.precision] + ([other_prec[args.precision]]
+                                if args.full and world == 1 and not args.single_precision else [])
     handles = {}
     for pr in precs:  # all handles and streams created once, up front: fixed HW-queue placement
         code = capi.RSPL_PREC_FP16 if pr in ("fp16", "fp16x3") else capi.RSPL_PREC_FP32  # SuperGlue
@@ -478,6 +498,50 @@ def main():
     trace_on = bool(trace_path)
     trace_out = []
     step_tr = []
+    last_lines = {}  # the newest step's line buffers and counts (--dump-outputs)
+
+    def dump_outputs(i, ba_res):
+        """--dump-outputs: what step i (the last timed step, complete on the device) handed to a caller, as
+        float64 DIR/<name>.npy.  Entries past a count (keypoints, lines) or without a valid flag are not written
+        by the step; they are zeroed here so that two runs compare output for output."""
+        d = pathlib.Path(args.dump_outputs)
+        if rank:
+            d = d / f"rank{rank}"
+        d.mkdir(parents=True, exist_ok=True)
+        slot, pslot = i % 3, (i - 1) % 3
+        n_cur = counts[slot].download((2,), np.int32)
+        n_prev = counts[pslot].download((2,), np.int32)
+        F = feats[slot].download((2, K, 259), np.float64)
+        for b in range(2):
+            F[b, n_cur[b]:] = 0.0
+        # SuperGlue pairs: (left(t), left(t-1)) and (left(t), right(t))
+        n0, n1 = (n_cur[0], n_cur[0]), (n_prev[0], n_cur[1])
+        sg_out = {}
+        for name, buf, dt, n in (("sg_indices0", outs[0], np.int32, n0), ("sg_indices1", outs[1], np.int32, n1),
+                                 ("sg_mscores0", outs[2], np.float64, n0), ("sg_mscores1", outs[3], np.float64, n1)):
+            a = buf.download((2, K), dt).astype(np.float64)
+            for p in range(2):
+                a[p, n[p]:] = 0.0
+            sg_out[name] = a
+        nl0, nl1 = min(last_lines["nl0"], 512), min(last_lines["nl1"], 512)
+        dl0, dl1 = last_lines["bufs"]
+        L0, L1 = dl0.download((512, 4), np.float64), dl1.download((512, 4), np.float64)
+        L0[nl0:] = 0.0
+        L1[nl1:] = 0.0
+        valid = lines_valid.download((512,), np.uint8)
+        valid[nl0:] = 0
+        Lr = lines_out.download((512, 4), np.float64)
+        Lr[valid == 0] = 0.0
+        arrays = {"sp_features": F, "sp_counts": n_cur.astype(np.float64), **sg_out,
+                  "lines_left": L0, "lines_right": L1, "line_counts": np.array([nl0, nl1], np.float64),
+                  "stereo_lines_right": Lr, "stereo_lines_valid": valid.astype(np.float64),
+                  "ba_pose_q": ba_res.pose_q, "ba_pose_p": ba_res.pose_p, "ba_points": ba_res.points,
+                  "ba_lines": ba_res.lines,
+                  "ba_chi2": np.array([ba_res.chi2_first, ba_res.chi2_second], np.float64),
+                  "ba_iterations": np.array([ba_res.iters_first, ba_res.iters_second], np.float64),
+                  **{f"ba_inlier_{k}": v.astype(np.float64) for k, v in ba_res.inlier.items()}}
+        for name, a in arrays.items():
+            np.save(d / f"{name}.npy", np.ascontiguousarray(a, np.float64))
 
     def measure(precision):
         """One full timed run of the pipeline at `precision`; returns its measurements."""
@@ -489,12 +553,12 @@ def main():
         ba_iters = []
         ba_err = []
         ba_q = queue.Queue(maxsize=2)
+        ba_outs = {}  # one result buffer per problem, reused (the bench reads the counters; --dump-outputs the rest)
 
         def tracking_thread():
             """BA worker: the reference runs LocalmapOptimization on the tracking thread while the
             feature thread keeps extracting/matching (src/map_builder.cc:48-49, src/map.cc:105-107)."""
             capi.check(capi.load().rspl_set_device(local), "rspl_set_device")  # HIP device is per thread
-            outs_ba = {}  # one result buffer per problem, reused (the bench reads only the counters)
             while True:
                 item = ba_q.get()
                 if item is None:
@@ -503,8 +567,8 @@ def main():
                 t = time.perf_counter()
                 try:
                     for prob in item:
-                        r = ba.run(prob, out=outs_ba.get(id(prob)))
-                        outs_ba[id(prob)] = r
+                        r = ba.run(prob, out=ba_outs.get(id(prob)))
+                        ba_outs[id(prob)] = r
                         ba_iters.append(r.iters_first + r.iters_second)
                 except Exception as e:  # surfaced on the main thread
                     ba_err.append(e)
@@ -515,7 +579,6 @@ def main():
         if not native:
             worker = threading.Thread(target=tracking_thread, daemon=True)
             worker.start()
-        outs_nat = {}  # native tracking thread: one result buffer per problem, reused
 
         def ba_put(item):
             """hand keyframe i's local BA to the tracking thread: the handle's native host thread
@@ -524,7 +587,7 @@ def main():
                 ba_q.put(item)
                 return
             for prob in item:
-                outs_nat[id(prob)] = ba.submit(prob, out=outs_nat.get(id(prob)))
+                ba_outs[id(prob)] = ba.submit(prob, out=ba_outs.get(id(prob)))
 
         def ba_drain():
             if not native:
@@ -535,7 +598,8 @@ def main():
                 per = len(ba_item(0))
                 ba_ms.extend([ms / n] * (n // per))
                 ba_iters.extend([its / n] * (n // per))
-        kt_steps = 0 if shard else args.ba_ktime_steps  # instrumented BA pass after the timed region
+        # instrumented BA pass after the timed region (--full only: it is a run of its own)
+        kt_steps = args.ba_ktime_steps if args.full and not shard else 0
         line_timers = []  # HIP-event timers around the line association (post stream), timed steps only
 
         def ba_item(i):
@@ -603,6 +667,7 @@ def main():
                 dl0, dl1 = line_bufs[slot]
                 nl0, t0ms = jobs[0].wait_device(dl0.ptr, 512, st_post.handle)
                 nl1, t1ms = jobs[1].wait_device(dl1.ptr, 512, st_post.handle)
+                last_lines.update(nl0=nl0, nl1=nl1, bufs=line_bufs[slot])
                 host_wait["lines"] += time.perf_counter() - tw
                 if trace_on:
                     step_tr[-1]["lines"] = time.perf_counter()
@@ -693,6 +758,9 @@ def main():
                                      for r in ba.trace()]})
         if ba_err:
             raise ba_err[0]
+        if args.dump_outputs and precision == args.precision:  # before any later pass reuses the buffers
+            i_last = args.warmup + args.steps - 1
+            dump_outputs(i_last, ba_outs[id(ba_item(i_last)[0])])
         # measurements of the timed region, read before the instrumented pass adds to them
         ba_ms_timed, ba_iters_timed = list(ba_ms), list(ba_iters)
         host_wait_timed = {k: round(v * 1e3 / args.steps, 4) for k, v in host_wait.items()}
@@ -820,7 +888,7 @@ def main():
                                        {"fp32": " (the bit-parity path)",
                                         "fp16x3": " (SuperPoint split fp16: the fp32 keypoint sets; SuperGlue fp16)",
                                         "fp16": ""}[oname]}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         nproc = os.cpu_count() or 1
         threads = min(16, nproc)  # the GPU box's CPU share is 16 cores per GPU
         frames = args.cpu_frames or (12 if args.workload == "c3" else 1)
