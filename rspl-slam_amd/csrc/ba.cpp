@@ -1,11 +1,13 @@
-// Local BA handle: C ABI (include/rspl.h) over ba_kernels.hip.
+// Local BA handle: C ABI (include/rspl.h) over the BA kernels (ba_first.hip, ba_schur.hip, ba_trial.hip).
 // Mirrors LocalmapOptimization (src/g2o_optimization/g2o_optimization.cc:21-252):
 //   optimize(10) with Huber kernels -> chi2/depth outlier levels, kernels removed ->
 //   initializeOptimization(0) + optimize(5) -> inlier flags -> write back T_wc, points, lines.
 // The Levenberg-Marquardt control (g2o OptimizationAlgorithmLevenberg: tau 1e-5,
-// good-step factor clamp [1/3, 2/3], ni doubling, 10 trials) runs on the host.  Each
-// trial is 3 kernels (Schur chunks; LDL^T solve + candidate poses; landmark update + cost,
-// see ba_kernels.hip); the last block of the cost kernel posts {chi2, scale, fail} and a
+// good-step factor clamp [1/3, 2/3], ni doubling, 10 trials) has two drivers: optimize_dev keeps it on
+// the device (ba::LmCtrl) and queues the trials back to back; optimize_host decides on the host, one
+// mailbox round trip per trial, for the landmark-sharded handle and windows beyond ba::fast_path.
+// A trial is 2-3 kernels (Schur chunks; LDL^T solve + candidate poses, fused into the chunks on small
+// windows; landmark update + cost); its last block posts {chi2, scale, fail} and a
 // sequence number to a pinned host-mapped mailbox that the host spins on (no stream
 // synchronisation, no D2H copy on the critical path).  Host->device traffic goes through
 // one pinned staging buffer (async copies only).
@@ -39,6 +41,13 @@ struct StagedCall;  // one call's host staging (below)
 }
 }  // namespace rspl
 
+// One bank of linearisation records.  Two alternate: bank[0] is the current set, bank[1] the spare one each
+// trial's candidate is linearised into speculatively, which becomes current by a swap when accepted.
+struct LinBank {
+  double *Hpp, *bp, *Hll, *bl, *Hpl;  // per edge (ba::Lin)
+  double *lm_Hll, *lm_bl;             // per landmark (ba::Sys::Hll / bl)
+};
+
 struct rspl_ba {
   rspl_ba_config cfg{};
   hipStream_t stream = nullptr;
@@ -46,14 +55,11 @@ struct rspl_ba {
   int maxE = 0, maxL = 0, maxK = 0, maxV = 0;
   // candidate state (ping-pong partners of the call buffer's T / X / L)
   double *Tb, *Xb, *Lb;
-  // per-edge linearisation records
-  double *err, *Hpp_e, *bp_e, *Hll_e, *bl_e, *Hpl_e;
-  // spare linearisation set (per-edge records + landmark blocks): each trial's candidate is
-  // linearised speculatively into it, and becomes current by a pointer swap when accepted
-  double *Hpp_s, *bp_s, *Hll_es, *bl_es, *Hpl_s, *Hll_s, *bl_s;
+  double* err;      // [E][4] per-edge errors (not banked)
+  LinBank bank[2];  // linearisation records: current, spare
   uint8_t* lm_act2;
   // system
-  double *Hll, *bl, *bp, *S, *x, *partial, *partial2;
+  double *bp, *S, *x, *partial, *partial2;
   unsigned* lm_ctr;  // [max_lines] line-landmark tickets (zeroed at create, re-armed by the kernel)
   unsigned long long* prof = nullptr;  // RSPL_BA_PROF: timing trace of one trial per call
   int prof_nb[5] = {0, 0, 0, 0, 0};    // its pair_chunk / update_errors grid sizes, group blocks, nchk, K
@@ -247,12 +253,13 @@ void carve(F& ar, rspl_ba* b) {
     else ar.template take<Tp>(n ? n : 1);
   };
   take(b->Tb, K * 8); take(b->Xb, nq * 3); take(b->Lb, nl * 6);
-  take(b->err, E * 4); take(b->Hpp_e, E * 21); take(b->bp_e, E * 6); take(b->Hll_e, E * 16);
-  take(b->bl_e, E * 4); take(b->Hpl_e, E * 24);
-  take(b->Hpp_s, E * 21); take(b->bp_s, E * 6); take(b->Hll_es, E * 16); take(b->bl_es, E * 4); take(b->Hpl_s, E * 24);
-  take(b->Hll_s, NL * 16); take(b->bl_s, NL * 4);
+  take(b->err, E * 4);
+  for (LinBank& k : b->bank) {
+    take(k.Hpp, E * 21); take(k.bp, E * 6); take(k.Hll, E * 16); take(k.bl, E * 4); take(k.Hpl, E * 24);
+  }
+  take(b->bank[1].lm_Hll, NL * 16); take(b->bank[1].lm_bl, NL * 4);
   take(b->lm_act2, NL);
-  take(b->Hll, NL * 16); take(b->bl, NL * 4); take(b->bp, K * 6);
+  take(b->bank[0].lm_Hll, NL * 16); take(b->bank[0].lm_bl, NL * 4); take(b->bp, K * 6);
   // block partials: edge-per-thread kernels (E / 256) and landmark-group kernels (NL * 8 / 256)
   const size_t nblk = std::max(E / 256, NL * 8 / 256) + 2;
   // partial also holds the setup kernel's per-block costs: the landmark groups plus the line
@@ -293,13 +300,15 @@ int ensure_stage(rspl_ba* b, int slot, size_t bytes, bool* grew = nullptr) {
   return RSPL_OK;
 }
 
-// Spin on the mailbox until the kernel chain tagged `seq` has posted; surface stream
-// errors and bound the wait.
-int wait_mail(rspl_ba* b, unsigned long long seq, double* v) {
+// Spin on the mailbox until accept() takes what it reads there.  Every 4096 spins: surface stream
+// errors, give up when the stream has gone idle without posting what accept() waits for (`what`, for
+// the message), and bound the wait to 60 s.
+template <typename Accept>
+int spin_mail(rspl_ba* b, const char* what, Accept&& accept) {
   using clk = std::chrono::steady_clock;
   const auto t0 = clk::now();
   for (unsigned it = 1;; it++) {
-    if (__atomic_load_n(&b->mail->seq, __ATOMIC_ACQUIRE) == seq) break;
+    if (accept()) return RSPL_OK;
     if ((it & 4095) == 0) {
       const hipError_t q = hipStreamQuery(b->stream);
       if (q != hipSuccess && q != hipErrorNotReady) {
@@ -307,21 +316,45 @@ int wait_mail(rspl_ba* b, unsigned long long seq, double* v) {
         return RSPL_E_DEVICE;
       }
       if (q == hipSuccess) {
-        if (__atomic_load_n(&b->mail->seq, __ATOMIC_ACQUIRE) == seq) break;
-        set_error("BA mailbox: stream idle but sequence %llu never posted", seq);
+        if (accept()) return RSPL_OK;
+        set_error("BA mailbox: stream idle but %s never posted", what);
         return RSPL_E_DEVICE;
       }
       if (clk::now() - t0 > std::chrono::seconds(60)) {
-        set_error("BA mailbox: timed out waiting for sequence %llu", seq);
+        set_error("BA mailbox: timed out waiting for %s", what);
         return RSPL_E_DEVICE;
       }
     }
     _mm_pause();
   }
+}
+
+// wait until the kernel chain tagged `seq` has posted; v: the four values it posted
+int wait_mail(rspl_ba* b, unsigned long long seq, double* v) {
+  char what[40];
+  snprintf(what, sizeof(what), "sequence %llu", seq);
+  const int rc = spin_mail(b, what, [&] { return __atomic_load_n(&b->mail->seq, __ATOMIC_ACQUIRE) == seq; });
+  if (rc) return rc;
   if (v) {
     volatile const double* mv = b->mail->v;
     for (int k = 0; k < 4; k++) v[k] = mv[k];
   }
+  return RSPL_OK;
+}
+
+// A grow-on-demand device buffer of the handle: at least `need` elements, `min_cap` when it grows.  The
+// stream may still read the old buffer, so it drains first; grew_bit goes into the call's trace flags.
+template <typename T>
+int grow_device(rspl_ba* b, T*& buf, size_t& cap, size_t need, size_t min_cap, unsigned grew_bit) {
+  if (need <= cap) return RSPL_OK;
+  RSPL_HIP(hipStreamSynchronize(b->stream));
+  if (buf) (void)hipFree(buf);
+  buf = nullptr;
+  cap = 0;
+  const size_t n = std::max(need, min_cap);
+  RSPL_HIP(hipMalloc((void**)&buf, sizeof(T) * n));
+  cap = n;
+  b->grew |= grew_bit;
   return RSPL_OK;
 }
 
@@ -438,17 +471,40 @@ void report_prof(rspl_ba* b) {
   (void)hipMemset(b->prof, 0, sizeof(unsigned long long) * ba::kProfLen);
 }
 
+// (Lin, Sys) views of the handle's banks: the current one into (Lr, S), the spare one into (Ls, Ss), which
+// otherwise copy them (the errors, the system and the control are shared)
+void view_bank(const LinBank& k, ba::Lin& L, ba::Sys& S) {
+  L.Hpp = k.Hpp; L.bp = k.bp; L.Hll = k.Hll; L.bl = k.bl; L.Hpl = k.Hpl;
+  S.Hll = k.lm_Hll; S.bl = k.lm_bl;
+}
+void bank_views(const rspl_ba* b, ba::Lin& Lr, ba::Sys& S, ba::Lin& Ls, ba::Sys& Ss) {
+  view_bank(b->bank[0], Lr, S);
+  Ls = Lr;
+  Ss = S;
+  view_bank(b->bank[1], Ls, Ss);
+}
+
 // an accepted candidate becomes the current state; with lin also its speculative linearisation
 void accept_swap(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, bool lin) {
   std::swap(P.T, P.Tn);
   std::swap(P.X, P.Xn);
   std::swap(P.L, P.Ln);
   if (!lin) return;
-  std::swap(b->Hpp_e, b->Hpp_s); std::swap(b->bp_e, b->bp_s); std::swap(b->Hll_e, b->Hll_es);
-  std::swap(b->bl_e, b->bl_es); std::swap(b->Hpl_e, b->Hpl_s);
-  std::swap(b->Hll, b->Hll_s); std::swap(b->bl, b->bl_s);
-  Lr.Hpp = b->Hpp_e; Lr.bp = b->bp_e; Lr.Hll = b->Hll_e; Lr.bl = b->bl_e; Lr.Hpl = b->Hpl_e;
-  S.Hll = b->Hll; S.bl = b->bl;
+  std::swap(b->bank[0], b->bank[1]);
+  view_bank(b->bank[0], Lr, S);
+}
+
+// RSPL_BA_PROF: trace the trial about to be queued with S (one per call) and note its grids and chunk
+// geometry for report_prof; the caller clears S.prof after the trial's launches
+void arm_prof(rspl_ba* b, const ba::Active& A, ba::Sys& S) {
+  if (!b->prof || b->prof_nb[0]) return;
+  S.prof = b->prof;
+  b->prof_A = A;
+  b->prof_nb[0] = ba::chunk_count(A);
+  b->prof_nb[1] = ba::update_errors_blocks(A) + A.n_lblk;
+  b->prof_nb[2] = ba::update_errors_blocks(A);
+  b->prof_nb[3] = A.nchk;
+  b->prof_nb[4] = A.K;
 }
 
 // the second optimize()'s setup launch queued right behind the first optimize()'s first batch of trials,
@@ -485,10 +541,21 @@ struct SpecFinish {
 // pointer view follows the device's current bank.
 void preupload_next(rspl_ba* b);
 
+// what only the device driver reads of an optimize() call
+struct DevLmArgs {
+  uint8_t* cls_level = nullptr;  // classify the edges into it first (the second optimize's levels)
+  bool build_pp = false;         // build the Schur chunks' edge-pair lists (see setup_dev)
+  SpecFinish* fin = nullptr;
+  SpecSetup* nxt = nullptr;
+  bool setup_done = false;       // its setup already ran from the speculative queue (SpecSetup)
+};
+
 int optimize_dev(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, const ba::Active& A, int iters,
-                 double* chi2_out, int* done_out, uint8_t* cls_level, bool build_pp, SpecFinish* fin,
-                 SpecSetup* nxt, bool setup_done) {
+                 double* chi2_out, int* done_out, const DevLmArgs& d) {
   hipStream_t st = b->stream;
+  uint8_t* const cls_level = d.cls_level;
+  SpecFinish* const fin = d.fin;
+  SpecSetup* const nxt = d.nxt;
   S.lm = b->lmctl;
   S.lm_slot = 0;
   static const bool trace = getenv("RSPL_BA_LMTRACE") != nullptr;
@@ -500,47 +567,28 @@ int optimize_dev(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, const ba::
   // errors, cost and linearisation at the current state (with cls_level: the second optimize's
   // outlier levels and landmark activity first) + computeLambdaInit into the control (slot 0);
   // nothing is posted: the host waits for the trials only
-  if (setup_done) {
+  if (d.setup_done) {
     // (queued behind the previous optimize()'s trials: SpecSetup)
   } else {
-    const size_t need = (size_t)ba::setup_pdg_len(A);
-    if (need > b->pdg_cap) {  // grow (the stream may still read the old buffer)
-      RSPL_HIP(hipStreamSynchronize(st));
-      if (b->pdg) (void)hipFree(b->pdg);
-      b->pdg = nullptr;
-      b->pdg_cap = 0;
-      const size_t cap = std::max(need, (size_t)1 << 14);
-      RSPL_HIP(hipMalloc((void**)&b->pdg, sizeof(double) * cap));
-      b->pdg_cap = cap;
-      b->grew |= 4;
-    }
+    int rg;
+    if ((rg = grow_device(b, b->pdg, b->pdg_cap, (size_t)ba::setup_pdg_len(A), (size_t)1 << 14, 4u))) return rg;
     ba::Sys Su = S;  // RSPL_BA_PROF: the first optimize's setup phases too
     Su.prof = b->prof && !b->prof_nb[0] && !cls_level ? b->prof : nullptr;
     RSPL_HIP(ba::setup_dev(P, Lr, A, Su, cls_level, cls_level ? const_cast<uint8_t*>(A.lm_act) : nullptr, iters,
-                           build_pp ? b->pp_cnt : nullptr, b->pp_off, b->pp_buf, b->pdg, st));
+                           d.build_pp ? b->pp_cnt : nullptr, b->pp_off, b->pp_buf, b->pdg, st));
   }
   unsigned long long q = b->seq;
   const unsigned long long q_first = b->seq + 1;
-  ba::Lin Ls = Lr;
-  Ls.Hpp = b->Hpp_s; Ls.bp = b->bp_s; Ls.Hll = b->Hll_es; Ls.bl = b->bl_es; Ls.Hpl = b->Hpl_s;
-  ba::Sys Ss = S;
-  Ss.Hll = b->Hll_s; Ss.bl = b->bl_s;
+  ba::Lin Ls;
+  ba::Sys Ss;
+  bank_views(b, Lr, S, Ls, Ss);
   int queued = 0;
   const int kev0 = b->kev_used;  // this optimize's first event triple
   auto enqueue = [&](int n) -> int {
     for (int k = 0; k < n; k++, queued++) {
       q = ++b->seq;
       ba::Spec sp{Ls, Ss};
-      const bool traced = b->prof && queued == 3 && !b->prof_nb[0];
-      if (traced) {
-        S.prof = b->prof;
-        b->prof_nb[0] = ba::chunk_count(A);
-        b->prof_A = A;
-        b->prof_nb[1] = ba::update_errors_blocks(A) + A.n_lblk;
-        b->prof_nb[2] = ba::update_errors_blocks(A);
-        b->prof_nb[3] = A.nchk;
-        b->prof_nb[4] = A.K;
-      }
+      if (queued == 3) arm_prof(b, A, S);
       S.lm_slot = queued & 1;
       S.lm_post = k == n - 1;
       hipEvent_t* ev = nullptr;
@@ -602,40 +650,25 @@ int optimize_dev(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, const ba::
   double v[4];
   for (;;) {
     // wait for the stopping trial (trials queued after it post nothing) or the last queued one
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    for (unsigned spin = 1;; spin++) {
-      // seqlock read: the next trial may be posting while we read; v is s1's iff vseq is still s1
-      const unsigned long long s1 = __atomic_load_n(&b->mail->seq, __ATOMIC_ACQUIRE);
-      if (s1 >= q_first && s1 <= q_last) {
-        volatile const double* mv = b->mail->v;
-        for (int k = 0; k < 4; k++) v[k] = mv[k];
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        if (__atomic_load_n(&b->mail->vseq, __ATOMIC_ACQUIRE) == s1 && (s1 == q_last || v[3] != 0.0)) break;
-      } else if (fin && s1 == fin->q) {  // the speculative finish already posted over the stopping trial's
-        volatile const double* mv = b->mail->v;  // seq (it posts only the seq: v / vseq stay the trial's)
-        for (int k = 0; k < 4; k++) v[k] = mv[k];
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        const unsigned long long vs = __atomic_load_n(&b->mail->vseq, __ATOMIC_ACQUIRE);
-        if (vs >= q_first && vs <= q_last && v[3] != 0.0) break;
-      }
-      if ((spin & 4095) == 0) {
-        const hipError_t e = hipStreamQuery(st);
-        if (e != hipSuccess && e != hipErrorNotReady) {
-          set_error("BA stream failed: %s", hipGetErrorString(e));
-          return RSPL_E_DEVICE;
-        }
-        if (e == hipSuccess && __atomic_load_n(&b->mail->seq, __ATOMIC_ACQUIRE) < q_first) {
-          set_error("BA mailbox: stream idle but no trial posted");
-          return RSPL_E_DEVICE;
-        }
-        if (clk::now() - t0 > std::chrono::seconds(60)) {
-          set_error("BA mailbox: timed out waiting for the LM trials");
-          return RSPL_E_DEVICE;
-        }
-      }
-      _mm_pause();
-    }
+    if ((rc = spin_mail(b, "the LM trials", [&] {
+          // seqlock read: the next trial may be posting while we read; v is s1's iff vseq is still s1
+          const unsigned long long s1 = __atomic_load_n(&b->mail->seq, __ATOMIC_ACQUIRE);
+          if (s1 >= q_first && s1 <= q_last) {
+            volatile const double* mv = b->mail->v;
+            for (int k = 0; k < 4; k++) v[k] = mv[k];
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);
+            return __atomic_load_n(&b->mail->vseq, __ATOMIC_ACQUIRE) == s1 && (s1 == q_last || v[3] != 0.0);
+          }
+          if (fin && s1 == fin->q) {  // the speculative finish already posted over the stopping trial's
+            volatile const double* mv = b->mail->v;  // seq (it posts only the seq: v / vseq stay the trial's)
+            for (int k = 0; k < 4; k++) v[k] = mv[k];
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);
+            const unsigned long long vs = __atomic_load_n(&b->mail->vseq, __ATOMIC_ACQUIRE);
+            return vs >= q_first && vs <= q_last && v[3] != 0.0;
+          }
+          return false;
+        })))
+      return rc;
     if (v[3] != 0.0) {
       if (b->ktime_on) {  // the trials up to the stopping one did work (later ones are no-ops)
         unsigned long long s1 = __atomic_load_n(&b->mail->seq, __ATOMIC_ACQUIRE);
@@ -659,18 +692,15 @@ bool dev_lm(const rspl_ba* b, const ba::Active& A, int iters) {
   return b->allreduce == nullptr && iters > 0 && ba::fast_path(A.K);
 }
 
-// one g2o SparseOptimizer::optimize(iters); device LM only: cls_level -- classify the edges into it
-// first (the second optimize's levels), build_pp -- build the Schur chunks' edge-pair lists (see
-// setup_dev); the caller does both itself otherwise
-int optimize(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, const ba::Active& A, int iters,
-             double* chi2_out, int* done_out, uint8_t* cls_level = nullptr, bool build_pp = false,
-             SpecFinish* fin = nullptr, SpecSetup* nxt = nullptr, bool setup_done = false) {
+// optimize(iters) with the LM control on the host, for what the device driver does not take: the
+// landmark-sharded handle (the ranks' all-reduces sit between a trial's kernels) and windows beyond
+// fast_path (global-memory Cholesky).  One mailbox round trip per trial.
+int optimize_host(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, const ba::Active& A, int iters,
+                  double* chi2_out, int* done_out) {
   hipStream_t st = b->stream;
   double v[4];
   int rc;
   const bool sh = b->allreduce != nullptr;
-  if (dev_lm(b, A, iters))
-    return optimize_dev(b, P, Lr, S, A, iters, chi2_out, done_out, cls_level, build_pp, fin, nxt, setup_done);
   const int n6 = 6 * A.K;
   double* so = b->red + n6 + b->nranks;  // this rank's {chi2, scale, fail} (S.shard_out)
   unsigned long long q = ++b->seq;
@@ -707,31 +737,18 @@ int optimize(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, const ba::Acti
         RSPL_HIP(ba::trial_solve(P, Lr, A, S, lambda, st));
         if ((rc = allreduce(b, so, 3))) return rc;
         RSPL_HIP(ba::shard_post(S, b->red, n6, b->nranks, 1, ba::fast_path(A.K) ? 1 : 0, q, st));
-      }
-      // speculative linearisation of the candidate into the spare set: the GPU runs it while the
-      // host reads the mailbox, so the next iteration's first kernel is already queued when the
-      // host decides (a rejected trial wastes it; the current set stays).  On the fast path it
-      // is fused into the trial's last kernel, otherwise queued behind the trial.
-      ba::Lin Ls = Lr;
-      Ls.Hpp = b->Hpp_s; Ls.bp = b->bp_s; Ls.Hll = b->Hll_es; Ls.bl = b->bl_es; Ls.Hpl = b->Hpl_s;
-      ba::Sys Ss = S;
-      Ss.Hll = b->Hll_s; Ss.bl = b->bl_s;
-      bool fused = false;
-      if (!sh) {
-          ba::Spec sp{Ls, Ss};
-        const bool traced = b->prof && it == 3 && qmax == 0 && !b->prof_nb[0];
-        if (traced) {
-          S.prof = sp.Ss.prof = b->prof;
-          b->prof_nb[0] = ba::chunk_count(A);
-          b->prof_A = A;
-        b->prof_A = A;
-          b->prof_nb[1] = ba::update_errors_blocks(A) + A.n_lblk;
-          b->prof_nb[2] = ba::update_errors_blocks(A);
-        }
-        RSPL_HIP(ba::trial(P, Lr, A, S, lambda, q, st, it + 1 < iters ? &sp : nullptr, &fused));
+      } else {
+        if (it == 3 && qmax == 0) arm_prof(b, A, S);
+        RSPL_HIP(ba::trial_host_large(P, Lr, A, S, lambda, q, st));
         S.prof = nullptr;
       }
-      if (it + 1 < iters && !fused) {
+      // speculative linearisation of the candidate into the spare set, queued behind the trial: the GPU
+      // runs it while the host reads the mailbox, so the next iteration's first kernel is already queued
+      // when the host decides (a rejected trial wastes it; the current set stays)
+      if (it + 1 < iters) {
+        ba::Lin Ls;
+        ba::Sys Ss;
+        bank_views(b, Lr, S, Ls, Ss);
         ba::Problem Pc = P;
         Pc.T = P.Tn; Pc.X = P.Xn; Pc.L = P.Ln;
         RSPL_HIP(ba::linearize(Pc, Ls, A, Ss, false, st));
@@ -767,6 +784,13 @@ int optimize(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, const ba::Acti
   *chi2_out = currentChi;
   *done_out = done;
   return RSPL_OK;
+}
+
+// one g2o SparseOptimizer::optimize(iters)
+int optimize(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, const ba::Active& A, int iters,
+             double* chi2_out, int* done_out, const DevLmArgs& d = {}) {
+  return dev_lm(b, A, iters) ? optimize_dev(b, P, Lr, S, A, iters, chi2_out, done_out, d)
+                             : optimize_host(b, P, Lr, S, A, iters, chi2_out, done_out);
 }
 
 }  // namespace
@@ -1318,16 +1342,7 @@ int run_call(rspl_ba* b, const ba::StagedCall& c, const rspl_ba_problem* pr, rsp
   int rc;
   tm.mark("run");
   b->grew = 0;
-  if (pair_bound > b->pp_cap) {  // grow the edge-pair lists (the stream is idle between calls)
-    RSPL_HIP(hipStreamSynchronize(st));
-    if (b->pp_buf) (void)hipFree(b->pp_buf);
-    b->pp_buf = nullptr;
-    b->pp_cap = 0;
-    const size_t cap = std::max(pair_bound, (size_t)1 << 16);
-    RSPL_HIP(hipMalloc((void**)&b->pp_buf, sizeof(int4) * cap));
-    b->pp_cap = cap;
-    b->grew |= 2;
-  }
+  if ((rc = grow_device(b, b->pp_buf, b->pp_cap, pair_bound, (size_t)1 << 16, 2u))) return rc;  // edge-pair lists
   // the call's inputs in one upload: a copy kernel reading the host-mapped staging slot over PCIe.  Not
   // hipMemcpyAsync: its H2D path stalled the first calls after the warmup by 7-10 ms each (the SDMA engine /
   // blit-kernel choice settling; profiles/r05_bench_20step_before.json), which cost the driver's 20-step bench
@@ -1358,10 +1373,10 @@ int run_call(rspl_ba* b, const ba::StagedCall& c, const rspl_ba_problem* pr, rsp
   }
   P.line_jac = b->line_jac;
   ba::Lin Lr{};
-  Lr.err = b->err; Lr.Hpp = b->Hpp_e; Lr.bp = b->bp_e; Lr.Hll = b->Hll_e; Lr.bl = b->bl_e;
-  Lr.Hpl = b->Hpl_e;
+  Lr.err = b->err;
   ba::Sys S{};
-  S.Hll = b->Hll; S.bl = b->bl; S.bp = b->bp; S.S = b->S; S.x = b->x; S.partial = b->partial;
+  view_bank(b->bank[0], Lr, S);
+  S.bp = b->bp; S.S = b->S; S.x = b->x; S.partial = b->partial;
   S.partial2 = b->partial2;
   S.out = reinterpret_cast<double*>(cb + cl.out);
   S.fail = reinterpret_cast<int*>(cb + cl.flags);
@@ -1427,8 +1442,10 @@ int run_call(rspl_ba* b, const ba::StagedCall& c, const rspl_ba_problem* pr, rsp
   nxt.level = level;
   nxt.iters2 = pr->iterations_second;
   const bool spec_setup = pp_fused && !sh && !b->ktime_on && dev_lm(b, nxt.A2, pr->iterations_second);
-  if ((rc = optimize(b, P, Lr, S, A, pr->iterations_first, &res->chi2_first, &res->iterations_done_first, nullptr,
-                     pp_fused, nullptr, spec_setup ? &nxt : nullptr)))
+  DevLmArgs d1;
+  d1.build_pp = pp_fused;
+  d1.nxt = spec_setup ? &nxt : nullptr;
+  if ((rc = optimize(b, P, Lr, S, A, pr->iterations_first, &res->chi2_first, &res->iterations_done_first, d1)))
     return rc;
   tm.mark("opt1");
   tr[5] = mono_s();
@@ -1462,9 +1479,11 @@ int run_call(rspl_ba* b, const ba::StagedCall& c, const rspl_ba_problem* pr, rsp
       fin.Xh = X_h;
       fin.Lh = L_h;
     }
-    if ((rc = optimize(b, P, Lr, S, A, pr->iterations_second, &res->chi2_second, &res->iterations_done_second,
-                       fused ? level : nullptr, false, spec_fin ? &fin : nullptr, nullptr,
-                       nxt.queued && !nxt.extra)))
+    DevLmArgs d2;
+    d2.cls_level = fused ? level : nullptr;
+    d2.fin = spec_fin ? &fin : nullptr;
+    d2.setup_done = nxt.queued && !nxt.extra;
+    if ((rc = optimize(b, P, Lr, S, A, pr->iterations_second, &res->chi2_second, &res->iterations_done_second, d2)))
       return rc;
     tm.mark("opt2");
     tr[6] = mono_s();
@@ -1478,14 +1497,7 @@ int run_call(rspl_ba* b, const ba::StagedCall& c, const rspl_ba_problem* pr, rsp
     // already queued (SpecFinish)
   } else if (sh) {  // owned landmarks + local edge flags gathered by one more all-reduce: complete on every rank
     const size_t glen = 3 * (size_t)nq + 6 * (size_t)nl + Eg;
-    if (glen > b->gcap) {
-      RSPL_HIP(hipStreamSynchronize(st));
-      if (b->gbuf) (void)hipFree(b->gbuf);
-      b->gbuf = nullptr;
-      b->gcap = 0;
-      RSPL_HIP(hipMalloc((void**)&b->gbuf, sizeof(double) * std::max<size_t>(glen, 1024)));
-      b->gcap = std::max<size_t>(glen, 1024);
-    }
+    if ((rc = grow_device(b, b->gbuf, b->gcap, glen, (size_t)1024, 0u))) return rc;
     RSPL_HIP(hipMemsetAsync(b->gbuf, 0, sizeof(double) * glen, st));
     RSPL_HIP(ba::shard_gather(P, Lr, E, reinterpret_cast<const int*>(cb + cl.gmap), b->rank, b->nranks, b->gbuf, st));
     if (glen && (rc = allreduce(b, b->gbuf, glen))) return rc;

@@ -190,7 +190,7 @@ hipError_t compute_errors(const Problem& P, const Lin& L, const Active& A, Sys& 
 hipError_t linearize(const Problem& P, const Lin& L, const Active& A, const Sys& S, bool with_maxdiag,
                      hipStream_t s);
 // mailbox post; with A, after linearize(with_maxdiag) it first folds the pose-block maxima in
-hipError_t post(Sys& S, unsigned long long seq, hipStream_t s, const Active* A = nullptr, int lm_iters = 0);
+hipError_t post(Sys& S, unsigned long long seq, hipStream_t s, const Active* A = nullptr);
 // the first pass of a device-LM optimize() (S.lm set, lm_iters > 0) in one launch: errors, robust
 // cost and linearisation at the current state, the pose / landmark diagonal maximum and the LM control
 // (computeLambdaInit) into S.lm[0].  level != null (the second optimize): the edges' outlier levels
@@ -207,15 +207,15 @@ hipError_t setup_dev(const Problem& P, const Lin& L, const Active& A, Sys& S, ui
                      const Lin* Ls = nullptr, const Sys* Ss = nullptr);
 int setup_pdg_len(const Active& A);
 // speculative linearisation of a trial's candidate into a spare record set, fused into the
-// trial's last kernel (fast path only)
+// trial's last kernel (trial_dev)
 struct Spec {
   Lin Ls;            // spare edge records (err shared with the current set)
   Sys Ss;            // spare landmark blocks Hll / bl
 };
-// one LM trial: Schur complement, Cholesky, back-substitution + candidate state, its cost;
-// with spec on the fast path also the candidate's linearisation (*fused = true)
-hipError_t trial(const Problem& P, const Lin& L, const Active& A, Sys& S, double lambda, unsigned long long seq,
-                 hipStream_t s, const Spec* spec, bool* fused);
+// one LM trial of the host driver on a window beyond fast_path (unsharded): Schur chunks, pose-pair sums and
+// Cholesky in global memory, back-substitution + candidate state, its cost posted with seq
+hipError_t trial_host_large(const Problem& P, const Lin& L, const Active& A, Sys& S, double lambda,
+                            unsigned long long seq, hipStream_t s);
 // one LM trial under device control (S.lm set, fast path): lambda, the current bank and the
 // accept / reject decision live in *S.lm; the trial's last kernel advances it and posts the mailbox
 // {chi2, iterations done, current bank, stop} + seq.  Always fused with the speculative linearisation
@@ -253,13 +253,15 @@ hipError_t shard_gather(const Problem& P, const Lin& L, int E, const int* gmap, 
 hipError_t shard_finish(const Problem& P, int E_global, const double* G, uint8_t* inl, double* Th, double* Xh,
                         double* Lh, Sys& S, unsigned long long seq, hipStream_t s);
 int shard_red_len(int K, int nranks);  // 6K + nranks + 3
-bool fast_path(int K);                 // the packed-LDS Schur/LDL^T path holds 6K
-bool wave_path(int K);                 // the single-wave LDL^T (fused into the Schur chunks) holds 6K
+// the reduced system is solved in one launch with the matrix on chip (single-wave, register or LDS solver by K:
+// launch_solve, ba_schur.hip) and the trial ends in update_errors_kernel; the device LM driver needs it
+bool fast_path(int K);
+bool wave_path(int K);                 // fast_path's smallest windows: the single-wave LDL^T holds 6K
 int update_blocks(const Problem& P);
 int errors_blocks(int Ea);
 int update_errors_blocks(const Active& A);
 // sets A.ue_bpr (after nchk / lmchunk): the trial's update workgroups on the XCD whose L2 the Schur chunks of
-// their landmarks just filled (RSPL_BA_UEXCD=0: plain order, A/B)
+// their landmarks just filled (0: plain order, when the ranges do not divide into whole workgroups)
 void set_update_geometry(Active& A);
 
 }  // namespace ba

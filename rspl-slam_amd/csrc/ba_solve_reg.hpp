@@ -1,7 +1,8 @@
 // Reduced camera system of the local BA for 10 < K <= 30 optimised poses (C5's 30-keyframe window, n = 6K = 174):
 // (S + lambda I) x = bp - sum Y bl from the pose-pair sums, in ONE 768-thread workgroup.  g2o solves the reduced
 // system with a dense factorisation (g2o_optimization.cc:26-36, BlockSolver + LinearSolverEigen); here a
-// right-looking LDL^T blocked by the 6x6 pose blocks, every pivot a reciprocal (v_rcp_f64 + two Newton steps).
+// right-looking LDL^T blocked by the 6x6 pose blocks, every pivot a reciprocal (v_rcp_f64 + one Newton step on
+// the pivot chain).
 //
 // Measured on gfx950 (tools/experiments/lat_bench.hip, s_memtime ticks): a dependent v_fma_f64 7.5, an independent
 // one 5.6 per wave instruction, v_mfma_f64_16x16x4f64 64 (1,024 FMAs), a workgroup barrier 15-20, an LDS round trip

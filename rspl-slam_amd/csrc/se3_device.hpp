@@ -1,4 +1,4 @@
-// SE3Quat pieces shared by the BA kernels (ba_kernels.hip, frame_kernels.hip): g2o's
+// SE3Quat pieces shared by the BA kernels (ba_device.hpp, frame_kernels.hip): g2o's
 // SE3Quat (q w x y z, t), its normalisation, product and exp map (update [omega; upsilon]).
 #pragma once
 #include <hip/hip_runtime.h>

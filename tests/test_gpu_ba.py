@@ -131,10 +131,11 @@ def test_localmap_optimization_mirror(weight_blobs):
     np.testing.assert_array_equal(np.array([c.inlier for c in stereo]), ref.inlier["stereo"].astype(bool))
 
 
-@pytest.mark.parametrize("n_poses", [23, 33, 36])
+@pytest.mark.parametrize("n_poses", [23, 31, 33, 36])
 def test_ba_many_poses(ba, n_poses):
-    # K = 32 optimised poses is the largest reduced system the LDS Schur/Cholesky path holds
-    # (n = 192, packed lower triangle); K = 35 takes the global-memory fallback
+    # K = n_poses - 1 optimised poses.  K = 22 and K = 30 take the register solver (schur_reg_kernel;
+    # 30 is its last size), K = 32 the packed-LDS solver (schur_solve_kernel: n = 192 is the largest
+    # lower triangle the LDS holds), K = 35 the host driver with the global-memory fallback
     # (pair_final + cholesky_kernel)
     prob, gt = SY.ba_problem(n_poses=n_poses, n_points=1500, n_lines=20, seed=40 + n_poses, pixel_sigma=0.8,
                              outlier_frac=0.05)
