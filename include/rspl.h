@@ -680,6 +680,108 @@ int rspl_lines_extract_wait_device(rspl_lines* h, double* d_lines, int capacity,
  * candidate, 1 none) for an H x W input, [H/2][W/2] each */
 int rspl_lines_debug_canny(rspl_lines* h, int H, int W, uint8_t* half, uint8_t* cls);
 
+/* ------------------------------------------------------------------------ */
+/* The tracking step itself: MapBuilder::TrackFrame + FramePoseOptimization  */
+/* (src/map_builder.cc:448-611) for a batch of independent frames, from      */
+/* SuperGlue's device indices to the pose and the track ids, as ONE          */
+/* stream-ordered chain of launches with no host work in between:            */
+/*   gather   mutual check (src/point_matching.cc:24-31), keyframe map-point */
+/*            lookup, the ordered compaction into PnP correspondences and    */
+/*            FrameOptimization edges, PnP's RANSAC subsets                  */
+/*   PnP      the kernels of rspl_pnp_solve (100 iterations, 20 px, 0.99)    */
+/*   seed     the 0.5 m / min_num_match gate (:517-521), T_wc -> T_cw        */
+/*   optimise the kernel of rspl_frame_optimize                              */
+/*   write-back  pose, track ids, kept matches (:586-608, :472-488)          */
+/* rspl_track_enqueue never waits for the device; rspl_track_fetch waits for */
+/* the one event the enqueue recorded.  Line tracking (MatchLines, :455,     */
+/* :490-501) stays with rspl_lines_match, fed from match_kf.                 */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  int max_batch;      /* frames per enqueue; also the number of keyframe slots */
+  int max_keypoints;  /* keypoints per frame and per keyframe */
+  int device;
+} rspl_track_config;
+
+#define RSPL_TRACK_NO_MAPPOINT 0   /* the keyframe keypoint has no map point */
+#define RSPL_TRACK_GOOD 1          /* Mappoint::IsValid (src/mappoint.cc:51) */
+#define RSPL_TRACK_NOT_GOOD 2      /* a map point that is not Good: matched, never an edge */
+
+typedef struct {
+  int slot;                     /* keyframe table (rspl_track_set_keyframe) */
+  const double* d_features;     /* DEVICE SuperPoint records [cap][259] of the current frame (x, y = rows 1, 2) */
+  const int32_t* d_n1;          /* DEVICE keypoint count of the current frame (clamped to max_keypoints) */
+  const int32_t* d_idx0;        /* DEVICE SuperGlue indices0 [n0]: keyframe -> current */
+  const int32_t* d_idx1;        /* DEVICE SuperGlue indices1 [n1]: current -> keyframe */
+  const double* d_u_right;      /* DEVICE [n1] right-image u (> 0: a stereo edge), or NULL: every edge is mono */
+  double fx, fy, cx, cy, bf;
+  double last_Twc[16];          /* _last_frame->GetPose(), row-major 4x4 */
+  double th_mono_point, th_stereo_point;  /* OptimizationConfig (tracking) */
+  int min_num_match;            /* keyframe.min_num_match (configs/configs_euroc.yaml:43: 10) */
+} rspl_track_frame;
+
+typedef struct {
+  double pose_q[4];             /* T_wc (x, y, z, w): the optimised pose when pose_set, else the last pose */
+  double pose_p[3];
+  int pose_set;                 /* n_inliers > min_num_match (:586) */
+  int n_inliers;                /* FrameOptimization's return value = TrackFrame's */
+  int n_pnp_inliers;            /* SolvePnPWithCV's return value */
+  int pnp_used;                 /* 1: PnP's pose seeded the optimisation, 0: the last pose did */
+  int n_keypoints;              /* the current frame's keypoint count as the device read it */
+  int n_matches;                /* mutual matches */
+  int n_kept;                   /* matches left after the removal of :472-488 */
+  int n_mono, n_stereo;         /* edges */
+  int rounds;                   /* as rspl_frame_result */
+  int iterations[4];
+  double chi2[4];
+  /* per current keypoint, caller arrays of max_keypoints entries (each may be NULL); the first
+   * n_keypoints are written */
+  int32_t* match_kf;            /* the mutual partner in the keyframe before filtering, or -1 */
+  int32_t* track_id;            /* the track id assigned (SetTrackId, :477), or -1.  As in the reference a
+                                 * match survives only with inliers[idx1] > 0, strictly: a match whose
+                                 * keyframe keypoint carries track id 0 is dropped */
+  uint8_t* kept;                /* 1: the match stays in `matches` */
+} rspl_track_result;
+
+/* debug (parity tests): the intermediate stages of frame `frame` of the last enqueue, read back
+ * after it completed.  Every pointer may be NULL.  K = max_keypoints. */
+typedef struct {
+  int n_corr;                   /* correspondences = edges */
+  int n_mono, n_stereo;
+  int32_t* corr_kp;             /* [K] PnP correspondence slot -> current keypoint (ascending) */
+  int32_t* edge_kp;             /* [K] edge slot -> current keypoint (mono first, then stereo) */
+  double* pnp_points;           /* [K][3] as PnP reads them (float-rounded) */
+  double* pnp_keypoints;        /* [K][2] */
+  double* edges;                /* [K][12] X[3], obs[3], cam[5], stereo -- the edge records */
+  int n_subsets;                /* RANSAC subsets generated (0 when n_corr < 8) */
+  int32_t* subsets;             /* [128][5] */
+  double pnp_Rwc[9], pnp_twc[3];
+  int pnp_n_inliers, pnp_hypotheses;
+  uint8_t* pnp_inlier;          /* [K] per correspondence slot */
+  double seed_q[4], seed_p[3];  /* the T_wc FrameOptimization started from (x, y, z, w) */
+  int pnp_used;
+  uint8_t* edge_inlier;         /* [K] FrameOptimization's flag per edge slot */
+} rspl_track_debug;
+
+typedef struct rspl_track rspl_track;
+
+int rspl_track_create(const rspl_track_config* cfg, rspl_track** out);
+void rspl_track_destroy(rspl_track* h);
+/* The keyframe's table for slot `slot` (0 <= slot < max_batch): per keypoint j < n0 its map point's
+ * world position points[3 j ..], state[j] (RSPL_TRACK_*) and track_id[j] (Frame::GetTrackId).  Host
+ * arrays, copied before the call returns; the upload is asynchronous on `stream` (NULL: the
+ * handle's), so enqueue on the same stream or order the streams with an event.  Call it again after
+ * a local BA moved the points. */
+int rspl_track_set_keyframe(rspl_track* h, int slot, int n0, const double* points, const uint8_t* state,
+                            const int32_t* track_id, void* stream);
+/* Enqueue the chain for frames[0 .. batch) on `stream` (NULL: the handle's; it may be the stream
+ * SuperGlue's outputs are produced on).  Everything the host knows (batch, slots, thresholds, NULL
+ * pointers) is checked before the first launch; device pointers are checked for NULL only.  No
+ * host synchronisation.  One enqueue is in flight per handle: fetch before the next. */
+int rspl_track_enqueue(rspl_track* h, int batch, const rspl_track_frame* frames, void* stream);
+/* Wait for the last enqueue and copy its results out: results[b] receives frame b. */
+int rspl_track_fetch(rspl_track* h, rspl_track_result* results);
+int rspl_track_debug_stage(rspl_track* h, int frame, rspl_track_debug* out);
+
 #ifdef __cplusplus
 }
 #endif

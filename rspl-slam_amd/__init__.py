@@ -10,7 +10,8 @@ from . import capi, weights, synthetic, ba_types, hostgroup, mapping, trajectory
 
 _API = ("SuperPoint", "SuperPointConfig", "SuperGlue", "SuperGlueConfig", "PointMatching",
         "LocalmapOptimization", "LocalBA", "FrameOptimization", "FrameBA",
-        "ShardGroup", "Comm", "comm_unique_id", "broadcast_comm_id", "PnP", "SolvePnPWithCV")
+        "ShardGroup", "Comm", "comm_unique_id", "broadcast_comm_id", "PnP", "SolvePnPWithCV",
+        "Tracker", "TrackFrame")
 
 
 def __getattr__(name):

@@ -562,3 +562,164 @@ def SolvePnPWithCV(K4, points, keypoints, point_ids=None):
 
 
 _default_pnp_cap = (0,)
+
+
+# ---------------------------------------------------------------------------
+# The tracking step: MapBuilder::TrackFrame + FramePoseOptimization (src/map_builder.cc:448-611)
+# ---------------------------------------------------------------------------
+TRACK_NO_MAPPOINT, TRACK_GOOD, TRACK_NOT_GOOD = 0, 1, 2  # RSPL_TRACK_*: the keyframe table's states
+
+
+class Tracker:
+    """Owns one rspl_track handle: SuperGlue's device indices -> pose, inliers and track ids for a batch
+    of independent frames as one stream-ordered chain of launches.  ``enqueue`` never waits for the
+    device; ``fetch`` waits for the one event it recorded."""
+
+    def __init__(self, max_batch=1, max_keypoints=1024, device=0):
+        if max_batch <= 0 or max_keypoints <= 0:  # before the library (and a device) is touched
+            raise ValueError(f"Tracker: max_batch {max_batch} and max_keypoints {max_keypoints} must be positive")
+        self.max_batch, self.max_keypoints = int(max_batch), int(max_keypoints)
+        self._lib = capi.load()
+        self._h = C.c_void_p()
+        cfg = capi.TrackConfig(self.max_batch, self.max_keypoints, device)
+        capi.check(self._lib.rspl_track_create(C.byref(cfg), C.byref(self._h)), "rspl_track_create")
+        self._batch = 0
+
+    def set_keyframe(self, slot, points, state, track_id, stream=None):
+        """The keyframe's table: per keypoint its map point's world position [n0, 3], state [n0]
+        (TRACK_*) and track id [n0].  Host arrays; the upload is asynchronous on ``stream``."""
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        st = np.ascontiguousarray(state, np.uint8).reshape(-1)
+        tid = np.ascontiguousarray(track_id, np.int32).reshape(-1)
+        if not (pts.shape[0] == st.shape[0] == tid.shape[0]):
+            raise ValueError("set_keyframe: points, state and track_id differ in length")
+        capi.check(self._lib.rspl_track_set_keyframe(self._h, slot, pts.shape[0], pts.ctypes.data, st.ctypes.data,
+                                                     tid.ctypes.data, _stream_handle(stream)),
+                   "rspl_track_set_keyframe")
+
+    def enqueue(self, frames, stream=None):
+        """frames: list of dicts with the device addresses ``d_features``, ``d_n1``, ``d_idx0``, ``d_idx1``
+        (ints or capi.DeviceBuffer), optional ``d_u_right``, ``slot`` (default 0), ``cam`` = (fx, fy, cx, cy,
+        bf), ``last_Twc`` [4, 4], and optional ``th_mono_point`` / ``th_stereo_point`` (5.991 / 7.815) and
+        ``min_num_match`` (10)."""
+        F = (capi.TrackFrameDesc * max(len(frames), 1))()
+        for f, d in zip(F, frames):
+            f.slot = d.get("slot", 0)
+            for k in ("d_features", "d_n1", "d_idx0", "d_idx1", "d_u_right"):
+                v = d.get(k)
+                setattr(f, k, v.ptr if isinstance(v, capi.DeviceBuffer) else v)
+            f.fx, f.fy, f.cx, f.cy, f.bf = [float(x) for x in d["cam"]]
+            f.last_Twc[:] = list(np.asarray(d["last_Twc"], np.float64).reshape(16))
+            f.th_mono_point = d.get("th_mono_point", 5.991)
+            f.th_stereo_point = d.get("th_stereo_point", 7.815)
+            f.min_num_match = d.get("min_num_match", 10)
+        capi.check(self._lib.rspl_track_enqueue(self._h, len(frames), F, _stream_handle(stream)), "rspl_track_enqueue")
+        self._batch = len(frames)
+
+    def fetch(self):
+        """Wait for the last enqueue.  Returns one dict per frame: pose_q (x, y, z, w), pose_p, pose_set,
+        n_inliers, n_pnp_inliers, pnp_used, n_keypoints, n_matches, n_kept, n_mono, n_stereo, rounds,
+        iterations, chi2 and, per current keypoint, match_kf, track_id, kept."""
+        if self._batch == 0:
+            return []
+        K = self.max_keypoints
+        R = (capi.TrackResult * self._batch)()
+        arrs = []
+        for r in R:
+            a = (np.full(K, -1, np.int32), np.full(K, -1, np.int32), np.zeros(K, np.uint8))
+            r.match_kf, r.track_id, r.kept = a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data
+            arrs.append(a)
+        capi.check(self._lib.rspl_track_fetch(self._h, R), "rspl_track_fetch")
+        out = []
+        for r, a in zip(R, arrs):
+            n = r.n_keypoints
+            out.append(dict(pose_q=np.array(r.pose_q[:]), pose_p=np.array(r.pose_p[:]), pose_set=bool(r.pose_set),
+                            n_inliers=r.n_inliers, n_pnp_inliers=r.n_pnp_inliers, pnp_used=bool(r.pnp_used),
+                            n_keypoints=n, n_matches=r.n_matches, n_kept=r.n_kept, n_mono=r.n_mono,
+                            n_stereo=r.n_stereo, rounds=r.rounds, iterations=tuple(r.iterations[:]),
+                            chi2=tuple(r.chi2[:]), match_kf=a[0][:n].copy(), track_id=a[1][:n].copy(),
+                            kept=a[2][:n].astype(bool)))
+        return out
+
+    def debug_stage(self, frame=0):
+        """The stages of frame ``frame`` of the last (fetched) enqueue, for the parity tests: the compacted
+        correspondences and edges, the RANSAC subsets, PnP's result, the seed pose and FrameOptimization's
+        per-edge flags."""
+        K = self.max_keypoints
+        D = capi.TrackDebug()
+        a = dict(corr_kp=np.zeros(K, np.int32), edge_kp=np.zeros(K, np.int32), pnp_points=np.zeros((K, 3)),
+                 pnp_keypoints=np.zeros((K, 2)), edges=np.zeros((K, 12)), subsets=np.zeros((128, 5), np.int32),
+                 pnp_inlier=np.zeros(K, np.uint8), edge_inlier=np.zeros(K, np.uint8))
+        for k, v in a.items():
+            setattr(D, k, v.ctypes.data)
+        capi.check(self._lib.rspl_track_debug_stage(self._h, frame, C.byref(D)), "rspl_track_debug_stage")
+        n = D.n_corr
+        return dict(n_corr=n, n_mono=D.n_mono, n_stereo=D.n_stereo, corr_kp=a["corr_kp"][:n], edge_kp=a["edge_kp"][:n],
+                    pnp_points=a["pnp_points"][:n], pnp_keypoints=a["pnp_keypoints"][:n], edges=a["edges"][:n],
+                    subsets=a["subsets"][:D.n_subsets], pnp_Rwc=np.array(D.pnp_Rwc[:]).reshape(3, 3),
+                    pnp_twc=np.array(D.pnp_twc[:]), pnp_n_inliers=D.pnp_n_inliers, pnp_hypotheses=D.pnp_hypotheses,
+                    pnp_inlier=a["pnp_inlier"][:n], seed_q=np.array(D.seed_q[:]), seed_p=np.array(D.seed_p[:]),
+                    pnp_used=bool(D.pnp_used), edge_inlier=a["edge_inlier"][:n])
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.rspl_track_destroy(self._h)
+            self._h = C.c_void_p()
+
+
+def _stream_handle(stream):
+    return stream.handle if isinstance(stream, capi.Stream) else stream
+
+
+_default_tracker = None
+
+
+def TrackFrame(frame0, frame1, matches, camera, last_Twc, cfg=None, min_num_match=10):
+    """Reference-shaped MapBuilder::TrackFrame (map_builder.cc:448-504) over host data, in place.
+
+    frame0: dict(points [n0, 3], state [n0], track_id [n0]) -- the keyframe's map points per keypoint;
+    frame1: dict(features [259, n1] as SuperPoint returns them, optional u_right [n1], track_id [n1] int
+    array, pose [4, 4]); matches: list of (queryIdx, trainIdx) into frame0 / frame1; camera = (fx, fy,
+    cx, cy, bf).  As the reference does it sets frame1["pose"] and frame1["track_id"][idx1] and erases
+    the matches that did not survive -- when more than min_num_match inliers are left -- and returns the
+    inlier count."""
+    global _default_tracker
+    F1 = np.ascontiguousarray(frame1["features"], np.float64)
+    n0, n1 = len(frame0["state"]), F1.shape[1]
+    cap = max(n0, n1, 1)
+    if _default_tracker is None or cap > _default_tracker.max_keypoints:
+        _default_tracker = Tracker(max_batch=1, max_keypoints=max(cap, 1024))
+    tr = _default_tracker
+    idx0 = np.full(max(n0, 1), -1, np.int32)
+    idx1 = np.full(max(n1, 1), -1, np.int32)
+    for q, t in matches:
+        idx0[q], idx1[t] = t, q
+    bufs = []
+
+    def dev(a):
+        b = capi.DeviceBuffer(max(a.nbytes, 8))
+        if a.nbytes:
+            b.upload(a)
+        bufs.append(b)
+        return b
+
+    fr = dict(d_features=dev(np.ascontiguousarray(F1.T)), d_n1=dev(np.array([n1], np.int32)), d_idx0=dev(idx0),
+              d_idx1=dev(idx1), cam=camera, last_Twc=last_Twc, min_num_match=min_num_match)
+    if frame1.get("u_right") is not None:
+        fr["d_u_right"] = dev(np.ascontiguousarray(frame1["u_right"], np.float64))
+    if cfg is not None:
+        fr["th_mono_point"], fr["th_stereo_point"] = cfg.mono_point, cfg.stereo_point
+    tr.set_keyframe(0, frame0["points"], frame0["state"], frame0["track_id"])
+    tr.enqueue([fr])
+    r = tr.fetch()[0]
+    if r["pose_set"]:
+        T = np.eye(4)
+        from .synthetic import quat_xyzw_to_R
+        T[:3, :3] = quat_xyzw_to_R(r["pose_q"])
+        T[:3, 3] = r["pose_p"]
+        frame1["pose"] = T
+        for q, t in matches:
+            if r["kept"][t]:
+                frame1["track_id"][t] = r["track_id"][t]
+        matches[:] = [(q, t) for q, t in matches if r["kept"][t]]
+    return r["n_inliers"]

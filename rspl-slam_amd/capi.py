@@ -45,6 +45,8 @@ EXPORTS = [
     "rspl_line_extract", "rspl_lines_create", "rspl_lines_destroy", "rspl_lines_assign", "rspl_lines_match",
     "rspl_lines_stereo", "rspl_lines_stereo_device", "rspl_lines_status", "rspl_lines_detect",
     "rspl_lines_debug_canny",
+    "rspl_track_create", "rspl_track_destroy", "rspl_track_set_keyframe", "rspl_track_enqueue", "rspl_track_fetch",
+    "rspl_track_debug_stage",
 ]
 
 
@@ -86,6 +88,36 @@ class PnpProblem(C.Structure):
 class PnpResult(C.Structure):
     _fields_ = [("Rwc", C.c_double * 9), ("twc", C.c_double * 3), ("inlier", C.POINTER(C.c_uint8)),
                 ("n_inliers", C.c_int), ("hypotheses", C.c_int)]
+
+
+class TrackConfig(C.Structure):
+    _fields_ = [("max_batch", C.c_int), ("max_keypoints", C.c_int), ("device", C.c_int)]
+
+
+class TrackFrameDesc(C.Structure):
+    _fields_ = [("slot", C.c_int), ("d_features", C.c_void_p), ("d_n1", C.c_void_p), ("d_idx0", C.c_void_p),
+                ("d_idx1", C.c_void_p), ("d_u_right", C.c_void_p),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("bf", C.c_double),
+                ("last_Twc", C.c_double * 16), ("th_mono_point", C.c_double), ("th_stereo_point", C.c_double),
+                ("min_num_match", C.c_int)]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [("pose_q", C.c_double * 4), ("pose_p", C.c_double * 3), ("pose_set", C.c_int),
+                ("n_inliers", C.c_int), ("n_pnp_inliers", C.c_int), ("pnp_used", C.c_int), ("n_keypoints", C.c_int),
+                ("n_matches", C.c_int), ("n_kept", C.c_int), ("n_mono", C.c_int), ("n_stereo", C.c_int),
+                ("rounds", C.c_int), ("iterations", C.c_int * 4), ("chi2", C.c_double * 4),
+                ("match_kf", C.c_void_p), ("track_id", C.c_void_p), ("kept", C.c_void_p)]
+
+
+class TrackDebug(C.Structure):
+    _fields_ = [("n_corr", C.c_int), ("n_mono", C.c_int), ("n_stereo", C.c_int),
+                ("corr_kp", C.c_void_p), ("edge_kp", C.c_void_p), ("pnp_points", C.c_void_p),
+                ("pnp_keypoints", C.c_void_p), ("edges", C.c_void_p), ("n_subsets", C.c_int),
+                ("subsets", C.c_void_p), ("pnp_Rwc", C.c_double * 9), ("pnp_twc", C.c_double * 3),
+                ("pnp_n_inliers", C.c_int), ("pnp_hypotheses", C.c_int), ("pnp_inlier", C.c_void_p),
+                ("seed_q", C.c_double * 4), ("seed_p", C.c_double * 3), ("pnp_used", C.c_int),
+                ("edge_inlier", C.c_void_p)]
 
 
 class RsplError(RuntimeError):
@@ -191,6 +223,14 @@ def load(path: pathlib.Path = LIB_PATH):
         lib.rspl_frame_optimize.argtypes = [vp, vp, ip, vp]
         lib.rspl_frame_destroy.argtypes = [vp]
         lib.rspl_frame_destroy.restype = None
+    if hasattr(lib, "rspl_track_create"):
+        lib.rspl_track_create.argtypes = [C.POINTER(TrackConfig), C.POINTER(vp)]
+        lib.rspl_track_destroy.argtypes = [vp]
+        lib.rspl_track_destroy.restype = None
+        lib.rspl_track_set_keyframe.argtypes = [vp, ip, ip, vp, vp, vp, vp]
+        lib.rspl_track_enqueue.argtypes = [vp, ip, vp, vp]
+        lib.rspl_track_fetch.argtypes = [vp, vp]
+        lib.rspl_track_debug_stage.argtypes = [vp, ip, C.POINTER(TrackDebug)]
     _lib = lib
     return lib
 

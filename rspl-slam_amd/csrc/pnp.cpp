@@ -47,12 +47,7 @@ struct Layout {
   }
 };
 
-// cv::RNG::next (multiply-with-carry) and RANSACPointSetRegistrator::getSubset
-inline unsigned rng_next(uint64_t& s) {
-  s = (uint64_t)(unsigned)s * 4164903690u + (unsigned)(s >> 32);
-  return (unsigned)s;
-}
-
+// RANSACPointSetRegistrator::getSubset over cv::RNG::next
 void subsets(int count, int iters, int32_t* idx) {
   uint64_t s = (uint64_t)-1;
   for (int h = 0; h < iters; h++) {
@@ -60,7 +55,7 @@ void subsets(int count, int iters, int32_t* idx) {
     for (int i = 0; i < 5; i++) {
       int v;
       for (;;) {
-        v = (int)(rng_next(s) % (unsigned)count);
+        v = (int)(pnp::rng_next(s) % (unsigned)count);
         bool dup = false;
         for (int j = 0; j < i; j++) dup |= o[j] == v;
         if (!dup) break;

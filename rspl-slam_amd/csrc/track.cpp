@@ -1,0 +1,379 @@
+// Tracking-step handle: C ABI (include/rspl.h, rspl_track_*) over track_kernels.hip, pnp_kernels.hip and
+// frame_kernels.hip.  Mirrors MapBuilder::TrackFrame + FramePoseOptimization (src/map_builder.cc:448-611)
+// for a batch of independent frames as one stream-ordered chain: gather | PnP (two kernels) | seed |
+// FrameOptimization | write-back, six launches and one event, no host work in between.  The solvers run
+// on this handle's own Args and buffers (pnp::solve / frame::optimize), all allocated at create.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "common.hpp"
+#include "track_kernels.hpp"
+
+using namespace rspl;
+
+struct rspl_track {
+  rspl_track_config cfg{};
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;
+  Arena arena;
+  track::Args ta{};
+  pnp::Args pa{};
+  frame::Args fa{};
+  // keyframe tables, one per slot: device arrays, their pinned upload staging and its event
+  double* kf_points = nullptr;
+  uint8_t* kf_state = nullptr;
+  int32_t* kf_tid = nullptr;
+  char* kf_stage = nullptr;
+  size_t kf_stage_slot = 0;
+  std::vector<hipEvent_t> kf_ev;
+  std::vector<int> n0;  // -1: the slot was never set
+  // host-mapped: the per-frame parameters in, the results out
+  track::Param* params = nullptr;
+  track::Out* out = nullptr;
+  int32_t *o_match_kf = nullptr, *o_track_id = nullptr;
+  uint8_t* o_kept = nullptr;
+  bool pending = false;
+  int batch = 0;  // frames of the last enqueue
+};
+
+namespace {
+
+// the raw draws of RANSAC's generator (csrc/pnp.cpp subsets()), which do not depend on the correspondence count
+std::vector<uint32_t> raw_draws(int n) {
+  std::vector<uint32_t> d(n);
+  uint64_t s = (uint64_t)-1;
+  for (int k = 0; k < n; k++) d[k] = pnp::rng_next(s);
+  return d;
+}
+
+// The draws kMaxIters subsets consume for `count` correspondences (getSubset: a duplicate draws again), or
+// -1 when the table ends first.
+int draws_needed(const std::vector<uint32_t>& d, int count) {
+  size_t pos = 0;
+  for (int h = 0; h < pnp::kMaxIters; h++) {
+    int o[5];
+    for (int i = 0; i < 5; i++) {
+      for (;;) {
+        if (pos >= d.size()) return -1;
+        const int v = (int)(d[pos++] % (unsigned)count);
+        bool dup = false;
+        for (int j = 0; j < i; j++) dup |= o[j] == v;
+        if (!dup) {
+          o[i] = v;
+          break;
+        }
+      }
+    }
+  }
+  return (int)pos;
+}
+
+struct Count {  // the size-only pass of the arena carving
+  size_t used = 0;
+  template <typename T>
+  T* take(size_t count) {
+    used = ((used + 255) & ~size_t(255)) + count * sizeof(T);
+    return nullptr;
+  }
+};
+
+template <typename T>
+int mapped(T** host, T** dev, size_t count) {
+  if (hipHostMalloc((void**)host, sizeof(T) * std::max<size_t>(count, 1), hipHostMallocMapped | hipHostMallocCoherent) !=
+          hipSuccess ||
+      hipHostGetDevicePointer((void**)dev, *host, 0) != hipSuccess)
+    return RSPL_E_DEVICE;
+  return RSPL_OK;
+}
+
+}  // namespace
+
+extern "C" int rspl_track_create(const rspl_track_config* cfg, rspl_track** out) {
+  RSPL_CHECK_ARG(cfg && out, "rspl_track_create: NULL argument");
+  *out = nullptr;
+  RSPL_CHECK_ARG(cfg->max_batch > 0 && cfg->max_keypoints > 0, "rspl_track_create: max_batch %d, max_keypoints %d",
+                 cfg->max_batch, cfg->max_keypoints);
+  RSPL_CHECK_ARG((size_t)cfg->max_batch * cfg->max_keypoints <= (size_t)1 << 28,
+                 "rspl_track_create: max_batch * max_keypoints too large");
+  // The draw table holds exactly what the worst count needs: the generator is deterministic, so the draws
+  // kMaxIters subsets consume are computed here for EVERY count an enqueue can meet (8 .. max_keypoints)
+  // and the maximum taken (count 8 rejects most: 4 of 8 values are duplicates for a subset's last index).
+  const int B = cfg->max_batch, K = cfg->max_keypoints;
+  std::vector<uint32_t> draws = raw_draws(track::kDrawCap);
+  int nd = 0;
+  for (int c = 8; c <= K; c++) {
+    const int need = draws_needed(draws, c);
+    RSPL_CHECK_ARG(need >= 0, "rspl_track_create: %d correspondences need more than %d RNG draws", c, track::kDrawCap);
+    nd = std::max(nd, need);
+  }
+  draws.resize(std::max(nd, 1));
+  RSPL_HIP(hipSetDevice(cfg->device));
+  auto* h = new rspl_track();
+  h->cfg = *cfg;
+  h->n0.assign(B, -1);
+  h->kf_ev.assign(B, nullptr);
+  const size_t E = (size_t)B * K;
+  track::Args& t = h->ta;
+  pnp::Args& p = h->pa;
+  frame::Args& f = h->fa;
+  uint32_t* d_draws = nullptr;
+  pnp::Out* pnp_out = nullptr;
+  frame::Out* frame_out = nullptr;
+  auto carve = [&](auto& A) {
+    d_draws = A.template take<uint32_t>(draws.size());
+    h->kf_points = A.template take<double>(3 * E);
+    h->kf_tid = A.template take<int32_t>(E);
+    h->kf_state = A.template take<uint8_t>(E);
+    t.params = A.template take<track::Param>(B);
+    t.pnp_desc = A.template take<pnp::Desc>(B);
+    t.pts = A.template take<double>(3 * E);
+    t.kps = A.template take<double>(2 * E);
+    t.subsets = A.template take<int32_t>((size_t)5 * pnp::kMaxIters * B);
+    t.frame_desc = A.template take<frame::Desc>(B);
+    t.edges = A.template take<frame::Edge>(E);
+    t.inl_in = A.template take<uint8_t>(E);
+    t.corr_kp = A.template take<int32_t>(E);
+    t.edge_kp = A.template take<int32_t>(E);
+    t.kp_edge = A.template take<int32_t>(E);
+    t.match_kf = A.template take<int32_t>(E);
+    t.inl_tid = A.template take<int32_t>(E);
+    t.counts = A.template take<int32_t>((size_t)4 * B);
+    t.seed = A.template take<track::Seed>(B);
+    p.inl = A.template take<uint8_t>(E);
+    pnp_out = A.template take<pnp::Out>(B);
+    p.hyp = A.template take<double>((size_t)12 * pnp::kMaxIters * B);
+    p.hcnt = A.template take<int>((size_t)pnp::kMaxIters * B);
+    f.err = A.template take<double>(4 * E);
+    f.level = A.template take<uint8_t>(E);
+    f.inl = A.template take<uint8_t>(E);
+    f.inl_out = A.template take<uint8_t>(E);
+    frame_out = A.template take<frame::Out>(B);
+  };
+  Count sz;
+  carve(sz);
+  int rc = h->arena.reserve(sz.used + 256);
+  if (rc) {
+    delete h;
+    return rc;
+  }
+  carve(h->arena);
+  h->kf_stage_slot = ((size_t)K * (3 * sizeof(double) + sizeof(int32_t) + 1) + 255) & ~size_t(255);
+  bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
+            hipEventCreateWithFlags(&h->done, hipEventDisableTiming) == hipSuccess &&
+            hipHostMalloc((void**)&h->kf_stage, h->kf_stage_slot * B, hipHostMallocDefault) == hipSuccess &&
+            mapped(&h->params, const_cast<track::Param**>(&t.host_params), B) == RSPL_OK &&
+            mapped(&h->out, &t.out, B) == RSPL_OK && mapped(&h->o_match_kf, &t.o_match_kf, E) == RSPL_OK &&
+            mapped(&h->o_track_id, &t.o_track_id, E) == RSPL_OK && mapped(&h->o_kept, &t.o_kept, E) == RSPL_OK;
+  for (int s = 0; ok && s < B; s++) ok = hipEventCreateWithFlags(&h->kf_ev[s], hipEventDisableTiming) == hipSuccess;
+  // (the scratch is zeroed once so that a debug read-back of slots no kernel wrote is defined)
+  ok = ok && hipMemset(h->arena.base, 0, h->arena.used) == hipSuccess &&
+       hipMemcpy(d_draws, draws.data(), sizeof(uint32_t) * draws.size(), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    set_error("rspl_track_create: stream / event / pinned allocation failed");
+    rspl_track_destroy(h);
+    return RSPL_E_DEVICE;
+  }
+  t.K = K;
+  t.draws = d_draws;
+  t.n_draws = nd;
+  t.pnp_out = pnp_out;
+  t.frame_out = frame_out;
+  t.edge_inl = f.inl_out;
+  p.frames = t.pnp_desc;
+  p.pts = t.pts;
+  p.kps = t.kps;
+  p.subsets = t.subsets;
+  p.out = pnp_out;
+  p.prof = nullptr;
+  f.frames = t.frame_desc;
+  f.edges = t.edges;
+  f.inl_in = t.inl_in;
+  f.out = frame_out;
+  *out = h;
+  return RSPL_OK;
+}
+
+extern "C" void rspl_track_destroy(rspl_track* h) {
+  if (!h) return;
+  if (h->pending && h->done) (void)hipEventSynchronize(h->done);
+  for (hipEvent_t e : h->kf_ev)
+    if (e) {
+      (void)hipEventSynchronize(e);
+      (void)hipEventDestroy(e);
+    }
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  h->arena.release();
+  if (h->kf_stage) (void)hipHostFree(h->kf_stage);
+  if (h->params) (void)hipHostFree(h->params);
+  if (h->out) (void)hipHostFree(h->out);
+  if (h->o_match_kf) (void)hipHostFree(h->o_match_kf);
+  if (h->o_track_id) (void)hipHostFree(h->o_track_id);
+  if (h->o_kept) (void)hipHostFree(h->o_kept);
+  if (h->done) (void)hipEventDestroy(h->done);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+}
+
+extern "C" int rspl_track_set_keyframe(rspl_track* h, int slot, int n0, const double* points, const uint8_t* state,
+                                       const int32_t* track_id, void* stream) {
+  RSPL_CHECK_ARG(h, "rspl_track_set_keyframe: NULL handle");
+  RSPL_CHECK_ARG(slot >= 0 && slot < h->cfg.max_batch, "slot %d outside [0, %d)", slot, h->cfg.max_batch);
+  RSPL_CHECK_ARG(n0 >= 0 && n0 <= h->cfg.max_keypoints, "n0 %d exceeds max_keypoints %d", n0, h->cfg.max_keypoints);
+  RSPL_CHECK_ARG(n0 == 0 || (points && state && track_id), "rspl_track_set_keyframe: NULL array");
+  RSPL_CHECK_ARG(!h->pending, "rspl_track_set_keyframe: an enqueue is in flight, fetch it first");
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  const size_t K = h->cfg.max_keypoints;
+  // the slot's staging may still feed an earlier upload: that copy (only it) is waited for
+  RSPL_HIP(hipEventSynchronize(h->kf_ev[slot]));
+  char* sg = h->kf_stage + h->kf_stage_slot * slot;
+  char* sg_tid = sg + 3 * sizeof(double) * K;
+  char* sg_state = sg_tid + sizeof(int32_t) * K;
+  if (n0) {
+    memcpy(sg, points, 3 * sizeof(double) * n0);
+    memcpy(sg_tid, track_id, sizeof(int32_t) * n0);
+    memcpy(sg_state, state, n0);
+    RSPL_HIP(hipMemcpyAsync(h->kf_points + 3 * K * slot, sg, 3 * sizeof(double) * n0, hipMemcpyHostToDevice, st));
+    RSPL_HIP(hipMemcpyAsync(h->kf_tid + K * slot, sg_tid, sizeof(int32_t) * n0, hipMemcpyHostToDevice, st));
+    RSPL_HIP(hipMemcpyAsync(h->kf_state + K * slot, sg_state, n0, hipMemcpyHostToDevice, st));
+    RSPL_HIP(hipEventRecord(h->kf_ev[slot], st));
+  }
+  h->n0[slot] = n0;
+  return RSPL_OK;
+}
+
+extern "C" int rspl_track_enqueue(rspl_track* h, int batch, const rspl_track_frame* frames, void* stream) {
+  RSPL_CHECK_ARG(h && (batch == 0 || frames), "rspl_track_enqueue: NULL argument");
+  RSPL_CHECK_ARG(batch >= 0 && batch <= h->cfg.max_batch, "batch %d exceeds max_batch %d", batch, h->cfg.max_batch);
+  RSPL_CHECK_ARG(!h->pending, "rspl_track_enqueue: the previous enqueue has not been fetched");
+  const size_t K = h->cfg.max_keypoints;
+  int max_n = 0;
+  for (int b = 0; b < batch; b++) {
+    const rspl_track_frame& fr = frames[b];
+    RSPL_CHECK_ARG(fr.slot >= 0 && fr.slot < h->cfg.max_batch && h->n0[fr.slot] >= 0,
+                   "frame %d: keyframe slot %d is not set", b, fr.slot);
+    RSPL_CHECK_ARG(fr.d_features && fr.d_n1 && fr.d_idx0 && fr.d_idx1, "frame %d: NULL device pointer", b);
+    RSPL_CHECK_ARG(fr.th_mono_point > 0 && fr.th_stereo_point > 0 && fr.min_num_match >= 0,
+                   "frame %d: bad thresholds", b);
+    bool finite = std::isfinite(fr.fx) && std::isfinite(fr.fy) && std::isfinite(fr.cx) && std::isfinite(fr.cy) &&
+                  std::isfinite(fr.bf);
+    for (int k = 0; k < 12; k++) finite = finite && std::isfinite(fr.last_Twc[k]);
+    RSPL_CHECK_ARG(finite && fr.fx != 0 && fr.fy != 0, "frame %d: bad camera or last pose", b);
+    // the edge count is the device's; its bound min(n0, max_keypoints) = n0 sizes the launch
+    max_n = std::max(max_n, h->n0[fr.slot]);
+  }
+  if (batch == 0) return RSPL_OK;
+  for (int b = 0; b < batch; b++) {
+    const rspl_track_frame& fr = frames[b];
+    track::Param& P = h->params[b];
+    P.feat = fr.d_features;
+    P.n1 = fr.d_n1;
+    P.idx0 = fr.d_idx0;
+    P.idx1 = fr.d_idx1;
+    P.u_right = fr.d_u_right;
+    P.kf_points = h->kf_points + 3 * K * fr.slot;
+    P.kf_state = h->kf_state + K * fr.slot;
+    P.kf_tid = h->kf_tid + K * fr.slot;
+    P.n0 = h->n0[fr.slot];
+    P.min_match = fr.min_num_match;
+    P.iters = 100;  // cv::solvePnPRansac(..., 100, 20.0, 0.99, ...) (g2o_optimization.cc:438-439)
+    P.pad = 0;
+    P.cam[0] = fr.fx; P.cam[1] = fr.fy; P.cam[2] = fr.cx; P.cam[3] = fr.cy; P.cam[4] = fr.bf;
+    P.thr2 = 20.0 * 20.0;
+    P.confidence = 0.99;
+    // const float deltaMonoPoint = sqrt(cfg.mono_point) (g2o_optimization.cc:279-280)
+    P.delta[0] = (double)(float)std::sqrt(fr.th_mono_point);
+    P.delta[1] = (double)(float)std::sqrt(fr.th_stereo_point);
+    P.th[0] = fr.th_mono_point;
+    P.th[1] = fr.th_stereo_point;
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) P.last[3 * r + c] = fr.last_Twc[4 * r + c];
+      P.last[9 + r] = fr.last_Twc[4 * r + 3];
+    }
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  RSPL_HIP(track::gather(h->ta, batch, st));
+  RSPL_HIP(pnp::solve(h->pa, batch, 100, st));
+  RSPL_HIP(track::seed(h->ta, batch, st));
+  RSPL_HIP(frame::optimize(h->fa, batch, max_n, st));
+  RSPL_HIP(track::write_back(h->ta, batch, st));
+  RSPL_HIP(hipEventRecord(h->done, st));
+  h->pending = true;
+  h->batch = batch;
+  return RSPL_OK;
+}
+
+extern "C" int rspl_track_fetch(rspl_track* h, rspl_track_result* res) {
+  RSPL_CHECK_ARG(h && res, "rspl_track_fetch: NULL argument");
+  RSPL_CHECK_ARG(h->pending, "rspl_track_fetch: nothing was enqueued");
+  RSPL_HIP(hipEventSynchronize(h->done));
+  h->pending = false;
+  const size_t K = h->cfg.max_keypoints;
+  for (int b = 0; b < h->batch; b++) {
+    const track::Out& o = h->out[b];
+    rspl_track_result& r = res[b];
+    memcpy(r.pose_q, o.q, sizeof(r.pose_q));
+    memcpy(r.pose_p, o.p, sizeof(r.pose_p));
+    r.pose_set = o.pose_set;
+    r.n_inliers = o.n_inliers;
+    r.n_pnp_inliers = o.n_pnp;
+    r.pnp_used = o.pnp_used;
+    r.n_keypoints = o.n1;
+    r.n_matches = o.n_matches;
+    r.n_kept = o.n_kept;
+    r.n_mono = o.n_mono;
+    r.n_stereo = o.n_stereo;
+    r.rounds = o.rounds;
+    memcpy(r.iterations, o.iters, sizeof(r.iterations));
+    memcpy(r.chi2, o.chi2, sizeof(r.chi2));
+    const size_t n = (size_t)std::min<int>(std::max(o.n1, 0), (int)K);
+    if (r.match_kf) memcpy(r.match_kf, h->o_match_kf + K * b, sizeof(int32_t) * n);
+    if (r.track_id) memcpy(r.track_id, h->o_track_id + K * b, sizeof(int32_t) * n);
+    if (r.kept) memcpy(r.kept, h->o_kept + K * b, n);
+  }
+  return RSPL_OK;
+}
+
+extern "C" int rspl_track_debug_stage(rspl_track* h, int frame, rspl_track_debug* d) {
+  RSPL_CHECK_ARG(h && d, "rspl_track_debug_stage: NULL argument");
+  RSPL_CHECK_ARG(!h->pending, "rspl_track_debug_stage: fetch the enqueue first");
+  RSPL_CHECK_ARG(frame >= 0 && frame < h->batch, "frame %d not in the last batch", frame);
+  const size_t K = h->cfg.max_keypoints, o = K * frame;
+  const track::Args& t = h->ta;
+  auto get = [](void* dst, const void* src, size_t bytes) {
+    return dst ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+  };
+  int32_t cn[4];
+  pnp::Desc pd;
+  pnp::Out po;
+  track::Seed sd;
+  RSPL_HIP(get(cn, t.counts + 4 * frame, sizeof(cn)));
+  RSPL_HIP(get(&pd, t.pnp_desc + frame, sizeof(pd)));
+  RSPL_HIP(get(&po, t.pnp_out + frame, sizeof(po)));
+  RSPL_HIP(get(&sd, t.seed + frame, sizeof(sd)));
+  d->n_corr = pd.n;
+  d->n_mono = cn[2];
+  d->n_stereo = cn[3];
+  d->n_subsets = pd.iters;
+  RSPL_HIP(get(d->corr_kp, t.corr_kp + o, sizeof(int32_t) * K));
+  RSPL_HIP(get(d->edge_kp, t.edge_kp + o, sizeof(int32_t) * K));
+  RSPL_HIP(get(d->pnp_points, t.pts + 3 * o, sizeof(double) * 3 * K));
+  RSPL_HIP(get(d->pnp_keypoints, t.kps + 2 * o, sizeof(double) * 2 * K));
+  RSPL_HIP(get(d->edges, t.edges + o, sizeof(frame::Edge) * K));
+  RSPL_HIP(get(d->subsets, t.subsets + (size_t)5 * pnp::kMaxIters * frame, sizeof(int32_t) * 5 * pnp::kMaxIters));
+  RSPL_HIP(get(d->pnp_inlier, h->pa.inl + o, K));
+  RSPL_HIP(get(d->edge_inlier, h->fa.inl_out + o, K));
+  memset(d->pnp_Rwc, 0, sizeof(d->pnp_Rwc));
+  memset(d->pnp_twc, 0, sizeof(d->pnp_twc));
+  if (po.n_inliers > 0) {
+    memcpy(d->pnp_Rwc, po.Rwc, sizeof(d->pnp_Rwc));
+    memcpy(d->pnp_twc, po.twc, sizeof(d->pnp_twc));
+  }
+  d->pnp_n_inliers = po.n_inliers;
+  d->pnp_hypotheses = po.hyps;
+  memcpy(d->seed_q, sd.q, sizeof(d->seed_q));
+  memcpy(d->seed_p, sd.p, sizeof(d->seed_p));
+  d->pnp_used = sd.pnp_used;
+  return RSPL_OK;
+}

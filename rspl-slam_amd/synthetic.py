@@ -270,6 +270,76 @@ def pnp_problem(n_points: int = 300, pixel_sigma: float = 0.8, outlier_frac: flo
     return np.array(cam, np.float64), X, kp, dict(Rwc=Rwc, twc=twc, outlier=out)
 
 
+def track_problem(n0: int = 400, n1: int = 400, n_common: int = 300, seed: int = 0, pixel_sigma: float = 0.3,
+                  outlier_frac: float = 0.1, stereo_frac: float = 0.0, frac_no_mappoint: float = 0.1,
+                  frac_not_good: float = 0.1, n_non_mutual: int = 8, last_rot: float = 0.01,
+                  last_trans: float = 0.05, width: int = 752, height: int = 480,
+                  cam=(EUROC_FX, EUROC_FY, EUROC_CX, EUROC_CY, EUROC_BF)):
+    """Seeded input of one tracking step (MapBuilder::TrackFrame, map_builder.cc:448-611): a keyframe of
+    ``n0`` keypoints matched by SuperGlue into a current frame of ``n1`` keypoints.
+
+    Keyframe table: per keypoint a world point, a state (0 no map point, 1 Good, 2 present but not Good;
+    ``frac_no_mappoint`` / ``frac_not_good`` of them) and a track id (j + 1, with a few 0 and -1).
+    Matches: ``n_common`` mutual pairs in a random permutation, ``n_non_mutual`` current keypoints whose
+    idx1 points at a keyframe keypoint that does not point back, as many keyframe keypoints likewise, and
+    one idx1 entry past n0; everything else -1.  A matched current keypoint is the projection of its
+    partner's world point from the ground-truth pose with ``pixel_sigma`` noise, ``outlier_frac`` of them
+    displaced by 30-80 px; ``stereo_frac`` of them carry a right-image u (> 0), the rest -1 (with
+    stereo_frac = 0 ``u_right`` is None: the reference's tracking frames are mono).  ``last_Twc`` is the
+    ground truth perturbed by ``last_rot`` rad / ``last_trans`` m.
+
+    Returns a dict: points [n0, 3], state [n0] uint8, track_id [n0] int32, idx0 [n0] int32, idx1 [n1]
+    int32, features [n1, 259] (the SuperPoint records: score, x, y, descriptor), u_right [n1] or None,
+    cam (fx, fy, cx, cy, bf), last_Twc [4, 4], gt = dict(Rwc, twc, outlier [n1] bool)."""
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy, bf = cam
+    n_common = min(n_common, n0, n1)
+    Rwc = _rotvec_to_R(rng.normal(0, 0.1, 3))
+    twc = rng.normal(0, 1.0, 3)
+    u, v = rng.uniform(0, width, n0), rng.uniform(0, height, n0)
+    z = rng.uniform(1.5, 20.0, n0)
+    X = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], 1) @ Rwc.T + twc
+    r = rng.uniform(size=n0)
+    state = np.where(r < frac_no_mappoint, 0, np.where(r < frac_no_mappoint + frac_not_good, 2, 1)).astype(np.uint8)
+    track_id = np.arange(1, n0 + 1, dtype=np.int32)
+    if n0 >= 4:
+        special = rng.choice(n0, max(2, n0 // 16), replace=False)
+        track_id[special[0::2]] = 0    # a valid track id the reference's `> 0` drops
+        track_id[special[1::2]] = -1   # no track yet
+    idx0, idx1 = np.full(n0, -1, np.int32), np.full(n1, -1, np.int32)
+    js, iis = rng.permutation(n0)[:n_common], rng.permutation(n1)[:n_common]
+    idx0[js], idx1[iis] = iis, js
+    feats = np.zeros((n1, 259))
+    feats[:, 0] = rng.uniform(0.01, 1.0, n1)
+    feats[:, 1], feats[:, 2] = rng.uniform(0, width, n1), rng.uniform(0, height, n1)
+    feats[:, 3:] = rng.normal(0, 1.0 / 16, (n1, 256))
+    outlier = np.zeros(n1, bool)
+    out = rng.uniform(size=n_common) < outlier_frac
+    px = np.stack([u[js], v[js]], 1) + rng.normal(0, pixel_sigma, (n_common, 2))
+    px[out] += rng.uniform(30, 80, (int(out.sum()), 2)) * rng.choice([-1, 1], (int(out.sum()), 2))
+    feats[iis, 1:3] = px
+    outlier[iis] = out
+    u_right = None
+    if stereo_frac > 0:
+        u_right = np.full(n1, -1.0)
+        ur = px[:, 0] - bf / z[js] + rng.normal(0, pixel_sigma, n_common)
+        st = (rng.uniform(size=n_common) < stereo_frac) & (ur > 0)
+        u_right[iis[st]] = ur[st]
+    # non-mutual entries: idx1[i] -> j with idx0[j] != i, idx0[j] -> i with idx1[i] != j, one idx1 past n0
+    free_i, free_j = np.flatnonzero(idx1 < 0), np.flatnonzero(idx0 < 0)
+    if n0 > 0:
+        for i in free_i[:n_non_mutual]:
+            idx1[i] = rng.integers(0, n0)
+        if len(free_i) > n_non_mutual:
+            idx1[free_i[n_non_mutual]] = n0 + 3
+    if n1 > 0:
+        for j in free_j[:n_non_mutual]:
+            idx0[j] = rng.integers(0, n1)
+    last = _Twc(_rotvec_to_R(rng.normal(0, last_rot, 3)) @ Rwc, twc + rng.normal(0, last_trans, 3))
+    return dict(points=X, state=state, track_id=track_id, idx0=idx0, idx1=idx1, features=feats, u_right=u_right,
+                cam=tuple(float(c) for c in cam), last_Twc=last, gt=dict(Rwc=Rwc, twc=twc, outlier=outlier))
+
+
 # ----------------------------------------------------------------------------
 # Synthetic keyframe sequence for the map-side local BA (Map::InsertKeyframe ->
 # Map::LocalMapOptimization, src/map.cc:24-118, :537-808)
