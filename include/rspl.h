@@ -136,6 +136,24 @@ int rspl_sp_debug_maps(rspl_sp* sp, int b, float* scores, float* desc);
  * score map [H][W] (any H, W within the arena) -> out [H][W]. */
 int rspl_sp_debug_nms(rspl_sp* sp, const float* scores, int height, int width, float* out);
 
+/* Test hook (RSPL_PREC_FP16 handles; otherwise RSPL_E_ARG): run ONE fp16 stage of the handle on host input,
+ * through the same launcher call with the same arguments as rspl_sp_infer_device, and copy its output back.
+ * height x width is the stage's OWN input level (the image for CONV1, the cell grid for the heads); fp16
+ * activations travel as float.
+ *   CONV1            in u8 [B][H][W]          -> out f32 [B][H/2][W/2][64]   (conv1a + conv1b + pool)
+ *   CONV2A .. CONVPD in f32 [B][H][W][Cin]    -> out f32 [B][H or H/2][W or W/2][Cout] (NHWC; 2B, 3B pool)
+ *   DET_HEAD         in f32 [B*H*W][512]      -> out f32 [B][8H][8W]         (dense score map)
+ *   TAPS             in cells as DET_HEAD, scores f32 [B][8H][8W], kp int32 [B][kp_stride] flat pixel indices
+ *                    (kp_counts[b] <= max_keypoints used) -> out f64 [B][max_keypoints][259], counts_out [B]
+ * scores / kp / kp_counts / counts_out are read for TAPS only (NULL otherwise). */
+enum {
+  RSPL_SP_LAYER_CONV1 = 0, RSPL_SP_LAYER_CONV2A, RSPL_SP_LAYER_CONV2B, RSPL_SP_LAYER_CONV3A, RSPL_SP_LAYER_CONV3B,
+  RSPL_SP_LAYER_CONV4A, RSPL_SP_LAYER_CONV4B, RSPL_SP_LAYER_CONVPD, RSPL_SP_LAYER_DET_HEAD, RSPL_SP_LAYER_TAPS
+};
+int rspl_sp_debug_layer(rspl_sp* sp, int stage, int batch, int height, int width, const void* in,
+                        const float* scores, const int32_t* kp, const int32_t* kp_counts, int kp_stride,
+                        void* out, int32_t* counts_out);
+
 /* Per-stage device time (HIP events on the launch stream) summed over the calls
  * made since rspl_sp_profile(sp, 1).  Stages: 0 conv1a+conv1b+pool (fused),
  * 1 conv2a..conv4b, 2 convPa|convDa, 3 1x1 heads (softmax/d2s, L2 norm),
@@ -188,7 +206,8 @@ int rspl_sg_infer_device2(rspl_sg* sg, int batch, const double* d_feat0, const i
                           int32_t* d_idx0, int32_t* d_idx1, double* d_ms0, double* d_ms1, void* stream,
                           void* post_stream);
 
-/* Log-assignment Z [(n0+1)*(n1+1)] f32 of the last call, pair p (for tests). */
+/* Log-assignment Z [(n0+1)*(n1+1)] f32 of the last call, pair p (for tests).  n0, n1 are the counts of the
+ * handle's last HOST call (rspl_sg_infer / rspl_pm_match): after a device-path call, size Z for those. */
 int rspl_sg_debug_scores(rspl_sg* sg, int p, float* Z);
 
 /* Sinkhorn health of the device paths.  The persistent log-Sinkhorn exchanges u / v between
@@ -208,6 +227,16 @@ int rspl_sg_debug_inject(rspl_sg* sg, int inject, unsigned spin_limit);
 int rspl_sg_debug_sinkhorn(rspl_sg* sg, const float* scores, int n0, int n1, float alpha, int iters, float* Z);
 int rspl_sg_debug_decode(rspl_sg* sg, const float* Z, int n0, int n1, int32_t* indices0, int32_t* indices1,
                          double* mscores0, double* mscores1);
+/* Test hook (RSPL_PREC_FP16 handles; otherwise RSPL_E_ARG): GNN layers [l0, l1) of the fp16 engine on host
+ * descriptors, launched exactly as rspl_sg_infer_device launches them (fp16 shadow of X, the q / k / v prologue
+ * with layer l0's weights, then one fused launch per layer, the same Q / K / V ping-pong parity), for the first
+ * `batch` pairs.  X is the handle's WHOLE token buffer, f32 [2 * max_batch][max_keypoints][256] (set 2p = image 0
+ * of pair p, 2p + 1 = image 1), uploaded, updated in place and copied back, so that a caller can see that nothing
+ * outside the pairs it ran was written.  n0 / n1: host counts [batch].  Q (may be NULL): the next layer's q of
+ * the batch's sets, fp16 bits [2 * batch][max_keypoints][256] (head-contiguous columns 64 h + d), written when
+ * l1 < 18. */
+int rspl_sg_debug_layers(rspl_sg* sg, int batch, float* X, const int32_t* n0, const int32_t* n1, int l0, int l1,
+                         uint16_t* Q);
 
 /* Stages: 0 prep + keypoint encoder, 1 18 GNN layers, 2 final_proj + scores + bins,
  * 3 hand-over to the post stream (queueing behind the previous call's post work; no kernel),

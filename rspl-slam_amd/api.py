@@ -90,6 +90,49 @@ class SuperPoint:
                    "rspl_sp_debug_nms")
         return out
 
+    LAYERS = ("conv1", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPD", "det_head", "taps")
+    _LAYER_IO = {"conv1": (1, 64, True), "conv2a": (64, 64, False), "conv2b": (64, 64, True), "conv3a": (64, 128, False),
+                 "conv3b": (128, 128, True), "conv4a": (128, 128, False), "conv4b": (128, 128, False),
+                 "convPD": (128, 512, False)}
+
+    def debug_layer(self, stage: str, x: np.ndarray, scores: Optional[np.ndarray] = None, keypoints=None):
+        """rspl_sp_debug_layer: one fp16 stage of an RSPL_PREC_FP16 handle on host input (fp16 values as float32).
+          conv1                 x u8 [B, H, W]              -> [B, H/2, W/2, 64]
+          conv2a .. convPD      x [B, H, W, Cin]            -> [B, H(/2), W(/2), Cout]
+          det_head              x cells [B, H8, W8, 512]    -> scores [B, 8 H8, 8 W8]
+          taps                  x cells, scores [B, 8 H8, 8 W8], keypoints = per image a list of flat pixel
+                                indices -> per image a feature block [n, 259] (float64)"""
+        st = self.LAYERS.index(stage)
+        B, H, W = x.shape[:3]
+        if stage in self._LAYER_IO:
+            cin, cout, pool = self._LAYER_IO[stage]
+            xin = np.ascontiguousarray(x, np.uint8 if stage == "conv1" else np.float32)
+            assert xin.shape == ((B, H, W) if stage == "conv1" else (B, H, W, cin)), xin.shape
+            out = np.empty((B, H // 2, W // 2, cout) if pool else (B, H, W, cout), np.float32)
+            capi.check(self._lib.rspl_sp_debug_layer(self._h, st, B, H, W, xin.ctypes.data, None, None, None, 0,
+                                                     out.ctypes.data, None), "rspl_sp_debug_layer")
+            return out
+        xin = np.ascontiguousarray(x, np.float32)
+        assert xin.shape == (B, H, W, 512), xin.shape
+        if stage == "det_head":
+            out = np.empty((B, 8 * H, 8 * W), np.float32)
+            capi.check(self._lib.rspl_sp_debug_layer(self._h, st, B, H, W, xin.ctypes.data, None, None, None, 0,
+                                                     out.ctypes.data, None), "rspl_sp_debug_layer")
+            return out
+        sc = np.ascontiguousarray(scores, np.float32)
+        assert sc.shape == (B, 8 * H, 8 * W) and len(keypoints) == B
+        stride = max(1, max(len(k) for k in keypoints))
+        kp = np.zeros((B, stride), np.int32)
+        cnt = np.array([len(k) for k in keypoints], np.int32)
+        for b, k in enumerate(keypoints):
+            kp[b, :len(k)] = k
+        out = np.empty((B, self._cap(), 259), np.float64)
+        cout = np.zeros(B, np.int32)
+        capi.check(self._lib.rspl_sp_debug_layer(self._h, st, B, H, W, xin.ctypes.data, sc.ctypes.data, kp.ctypes.data,
+                                                 cnt.ctypes.data, stride, out.ctypes.data, cout.ctypes.data),
+                   "rspl_sp_debug_layer")
+        return [out[b, :cout[b]].copy() for b in range(B)], cout
+
     def debug_maps(self, b: int, height: int, width: int):
         s = np.empty((height, width), np.float32)
         d = np.empty((256, height // 8, width // 8), np.float32)
@@ -205,6 +248,20 @@ class SuperGlue:
         capi.check(self._lib.rspl_sg_debug_decode(self._h, z.ctypes.data, n0, n1, i0.ctypes.data, i1.ctypes.data,
                                                   m0.ctypes.data, m1.ctypes.data), "rspl_sg_debug_decode")
         return i0, i1, m0, m1
+
+    def debug_layers(self, batch: int, X: np.ndarray, n0, n1, l0: int, l1: int):
+        """rspl_sg_debug_layers: GNN layers [l0, l1) of the fp16 engine on host descriptors X
+        [2 * max_batch, max_keypoints, 256] (the handle's whole token buffer; the first `batch` pairs run).
+        Returns (X after the layers, the next layer's q [2 * batch, max_keypoints, 256] float16 or None)."""
+        c = self.config
+        Xio = np.array(X, np.float32, order="C")
+        assert Xio.shape == (2 * max(1, c.max_batch), c.max_keypoints, 256), Xio.shape
+        a0, a1 = np.ascontiguousarray(n0, np.int32), np.ascontiguousarray(n1, np.int32)
+        assert a0.shape == (batch,) and a1.shape == (batch,)
+        Q = np.zeros((2 * batch, c.max_keypoints, 256), np.float16) if l1 < 18 else None
+        capi.check(self._lib.rspl_sg_debug_layers(self._h, batch, Xio.ctypes.data, a0.ctypes.data, a1.ctypes.data, l0, l1,
+                                                  Q.ctypes.data if Q is not None else None), "rspl_sg_debug_layers")
+        return Xio, Q
 
     @property
     def handle(self):

@@ -266,6 +266,35 @@ sg::GemmArgs G_(const float* A, int lda, const float* B, int ldb, const float* b
 
 }  // namespace
 
+// RSPL_PREC_FP16 GNN: the LayerArgs of the q / k / v prologue of layer l and of the fused layer l, and the chain
+// [l0, l1) (prologue of l0, then one launch per layer), shared by rspl_sg_infer_device ([0, 18)) and
+// rspl_sg_debug_layers.  Q / K / V ping-pong by layer parity: layer l reads set l & 1 and writes set (l + 1) & 1.
+static sg::LayerArgs gnn_prologue_args(const rspl_sg* s, int l, const int* d_n0, const int* d_n1) {
+  sg::LayerArgs la{};
+  la.Qn = s->Qf[l & 1]; la.Kn = s->Kf[l & 1]; la.Vn = s->Vf[l & 1];
+  la.X = s->X; la.Xh = s->Xh;
+  la.Wq = s->fwqkv + (size_t)l * 256 * 768; la.bq = s->bqkv + (size_t)l * 768;
+  la.n0 = d_n0; la.n1 = d_n1; la.nmax = s->nmax; la.nt = s->ldv / 32; la.qkv_only = 1;
+  return la;
+}
+static sg::LayerArgs gnn_layer_args(const rspl_sg* s, int l, const int* d_n0, const int* d_n1) {
+  sg::LayerArgs la{};
+  la.Qc = s->Qf[l & 1]; la.Kc = s->Kf[l & 1]; la.Vc = s->Vf[l & 1];
+  la.Qn = s->Qf[(l + 1) & 1]; la.Kn = s->Kf[(l + 1) & 1]; la.Vn = s->Vf[(l + 1) & 1];
+  la.X = s->X; la.Xh = s->Xh;
+  la.W1 = s->fw1 + (size_t)l * 512 * 512; la.b1 = s->b1m + (size_t)l * 512;
+  la.W2 = s->fw2 + (size_t)l * 512 * 256; la.b2 = s->b2 + (size_t)l * 256;
+  const int ln = std::min(l + 1, kLayers - 1);
+  la.Wq = s->fwqkv + (size_t)ln * 256 * 768; la.bq = s->bqkv + (size_t)ln * 768;
+  la.n0 = d_n0; la.n1 = d_n1; la.nmax = s->nmax; la.nt = s->ldv / 32; la.cross = l & 1; la.last = l == kLayers - 1;
+  return la;
+}
+static int run_gnn_h(rspl_sg* s, int B, int l0, int l1, const int* d_n0, const int* d_n1, hipStream_t st) {
+  RSPL_HIP(sg::gnn_layer(gnn_prologue_args(s, l0, d_n0, d_n1), B, st));
+  for (int l = l0; l < l1; l++) RSPL_HIP(sg::gnn_layer(gnn_layer_args(s, l, d_n0, d_n1), B, st));
+  return RSPL_OK;
+}
+
 // log_optimal_transport (superglue.py:185-205) on the couplings of B pairs, on stream st
 static hipError_t run_sinkhorn(rspl_sg* s, const float* cpl, float* Zp, const int* cn0, const int* cn1, int B,
                                int iters, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
@@ -484,38 +513,11 @@ extern "C" int rspl_sg_infer_device2(rspl_sg* s, int B, const double* d_feat0, c
   // AttentionalGNN (superglue.py:165-173): ['self', 'cross'] * 9; both images read pre-layer descs
   if (h16) {  // fp16 activations end to end (X itself stays fp32: the residual stream)
     RSPL_HIP(sg::to_half(s->X, s->Xh, (size_t)T * 256, st));
-    auto gh = [&](const _Float16* A, int lda, const _Float16* W, int N, int K, const float* bias) {
-      sg::GemmHArgs g{};
-      g.A = A; g.lda = lda; g.ksplit = K; g.B = W; g.ldb = K; g.bias = bias; g.M = T; g.N = N; g.K = K;
-      g.nmax = nm; g.ldv = s->ldv;
-      return g;
-    };
     // one launch per layer on one workgroup per 32-token tile (layer_kernel).  (Four launches per layer --
     // QKV GEMM, attention, mlp.0, mlp.3 -- were slower and were removed in round 6; round 5 measured the layer on
     // four workgroups per tile -- the same bits, slower in the pipeline: profiles/r05_experiments.md.)
-    auto layer = [&](sg::LayerArgs& la, int) { return sg::gnn_layer(la, B, st); };
-    {  // layer 0's q / k / v (prologue launch), then one fused launch per layer
-      {
-        sg::LayerArgs la{};
-        la.Qn = s->Qf[0]; la.Kn = s->Kf[0]; la.Vn = s->Vf[0];
-        la.X = s->X; la.Xh = s->Xh;
-        la.Wq = s->fwqkv; la.bq = s->bqkv;
-        la.n0 = d_n0; la.n1 = d_n1; la.nmax = nm; la.nt = s->ldv / 32; la.qkv_only = 1;
-        RSPL_HIP(layer(la, -1));
-      }
-      for (int l = 0; l < kLayers; l++) {
-        sg::LayerArgs la{};
-        la.Qc = s->Qf[l & 1]; la.Kc = s->Kf[l & 1]; la.Vc = s->Vf[l & 1];
-        la.Qn = s->Qf[(l + 1) & 1]; la.Kn = s->Kf[(l + 1) & 1]; la.Vn = s->Vf[(l + 1) & 1];
-        la.X = s->X; la.Xh = s->Xh;
-        la.W1 = s->fw1 + (size_t)l * 512 * 512; la.b1 = s->b1m + (size_t)l * 512;
-        la.W2 = s->fw2 + (size_t)l * 512 * 256; la.b2 = s->b2 + (size_t)l * 256;
-        const int ln = std::min(l + 1, kLayers - 1);
-        la.Wq = s->fwqkv + (size_t)ln * 256 * 768; la.bq = s->bqkv + (size_t)ln * 768;
-        la.n0 = d_n0; la.n1 = d_n1; la.nmax = nm; la.nt = s->ldv / 32; la.cross = l & 1; la.last = l == kLayers - 1;
-        RSPL_HIP(layer(la, l));
-      }
-    }
+    // layer 0's q / k / v (prologue launch), then one fused launch per layer
+    if (int rc = run_gnn_h(s, B, 0, kLayers, d_n0, d_n1, st)) return rc;
   }
   for (int l = 0; l < kLayers && !h16; l++) {
     RSPL_HIP(sg::gemm(G_(s->X, 256, s->wqkv + (size_t)l * 256 * 768, 768, s->bqkv + (size_t)l * 768, s->QKV, 768, T,
@@ -763,5 +765,30 @@ extern "C" int rspl_sg_debug_decode(rspl_sg* s, const float* Z, int n0, int n1, 
   RSPL_HIP(hipMemcpyAsync(mscores1, s->ms1, sizeof(double) * n1, hipMemcpyDeviceToHost, st));
   RSPL_HIP(hipStreamSynchronize(st));
   s->last_B = 0;
+  return RSPL_OK;
+}
+
+extern "C" int rspl_sg_debug_layers(rspl_sg* s, int B, float* X, const int32_t* n0, const int32_t* n1, int l0, int l1,
+                                    uint16_t* Q) {
+  RSPL_CHECK_ARG(s && X && n0 && n1, "rspl_sg_debug_layers: NULL argument");
+  RSPL_CHECK_ARG(s->cfg.precision == RSPL_PREC_FP16, "rspl_sg_debug_layers: the handle must be RSPL_PREC_FP16");
+  RSPL_CHECK_ARG(B >= 1 && B <= s->B && l0 >= 0 && l0 < l1 && l1 <= kLayers, "batch %d / layers [%d, %d) out of range", B,
+                 l0, l1);
+  for (int p = 0; p < B; p++)
+    RSPL_CHECK_ARG(n0[p] >= 0 && n0[p] <= s->nmax && n1[p] >= 0 && n1[p] <= s->nmax, "counts of pair %d outside [0, %d]", p,
+                   s->nmax);
+  hipStream_t st = s->stream;
+  if (int rc = sync_all(s)) return rc;
+  const size_t n = (size_t)s->B * 2 * s->nmax * 256;  // the handle's whole token buffer: max_batch pairs
+  RSPL_HIP(hipMemcpyAsync(s->X, X, sizeof(float) * n, hipMemcpyHostToDevice, st));
+  RSPL_HIP(hipMemcpyAsync(s->n0, n0, sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
+  RSPL_HIP(hipMemcpyAsync(s->n1, n1, sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
+  RSPL_HIP(sg::to_half(s->X, s->Xh, (size_t)B * 2 * s->nmax * 256, st));
+  if (int rc = run_gnn_h(s, B, l0, l1, s->n0, s->n1, st)) return rc;
+  RSPL_HIP(hipMemcpyAsync(X, s->X, sizeof(float) * n, hipMemcpyDeviceToHost, st));
+  if (Q && l1 < kLayers)
+    RSPL_HIP(hipMemcpyAsync(Q, s->Qf[l1 & 1], sizeof(uint16_t) * (size_t)B * 2 * s->nmax * 256, hipMemcpyDeviceToHost, st));
+  RSPL_HIP(hipStreamSynchronize(st));
+  s->last_B = 0;  // the debug call reused the batch's buffers
   return RSPL_OK;
 }

@@ -262,6 +262,48 @@ int nms_topk(rspl_sp* s, int B, int H, int W, int k, hipStream_t st) {
   RSPL_HIP(topk(t, B, st));
   return RSPL_OK;
 }
+
+// RSPL_PREC_FP16: the eight 3x3 conv launches (conv1a+1b+pool, conv2a, conv2b+pool, conv3a, conv3b+pool, conv4a,
+// conv4b, convPa | convDa) and the two head launches, each with its whole argument set-up, shared by
+// rspl_sp_infer_device and rspl_sp_debug_layer so that the test hook launches what the product launches.
+constexpr int kH16Convs = 8;
+struct H16Conv { const _Float16* hw; const float* bias; int cin, cout; bool pool; };
+
+H16Conv h16_conv_desc(const rspl_sp* s, int i) {
+  const H16Conv tab[kH16Convs] = {{s->hw1b, s->b1b, 64, 64, true},    {s->hw2a, s->b2a, 64, 64, false},
+                                  {s->hw2b, s->b2b, 64, 64, true},    {s->hw3a, s->b3a, 64, 128, false},
+                                  {s->hw3b, s->b3b, 128, 128, true},  {s->hw4a, s->b4a, 128, 128, false},
+                                  {s->hw4b, s->b4b, 128, 128, false}, {s->hwPD, s->bPD, 128, 512, false}};
+  return tab[i];
+}
+// activations ping-pong actA / actB (conv1 writes actA); convPa | convDa writes the cells
+const _Float16* h16_conv_in(const rspl_sp* s, int i) {
+  return i == 0 ? nullptr : reinterpret_cast<const _Float16*>(i & 1 ? s->actA : s->actB);
+}
+_Float16* h16_conv_out(const rspl_sp* s, int i) {
+  return reinterpret_cast<_Float16*>(i == kH16Convs - 1 ? s->cells : (i & 1 ? s->actB : s->actA));
+}
+// stage i at its own input level H x W; c carries the image / conv1a fields (stage 0 only)
+hipError_t h16_conv(const rspl_sp* s, int i, sp::ConvArgs c, int H, int W, int B, hipStream_t st, hipEvent_t t0 = nullptr,
+                    hipEvent_t t1 = nullptr) {
+  const H16Conv d = h16_conv_desc(s, i);
+  c.H = H; c.W = W; c.cout = d.cout; c.hin = h16_conv_in(s, i); c.hw = d.hw; c.bias = d.bias; c.hout = h16_conv_out(s, i);
+  return sp::conv3x3_h(c, d.cin, d.pool, i == 0, false, B, st, t0, t1);
+}
+sp::HeadHArgs h16_head(const rspl_sp* s, int B, int P, int W8) {
+  sp::HeadHArgs h{};
+  h.cells = reinterpret_cast<const _Float16*>(s->cells); h.wPb = s->fwPb; h.bPb = s->bPb; h.scores = s->scores;
+  h.B = B; h.P = P; h.W8 = W8;
+  return h;
+}
+sp::TapArgs h16_taps(const rspl_sp* s, double* d_features, int capacity, int32_t* d_counts, int B, int H, int W) {
+  const int k = s->cfg.max_keypoints;
+  sp::TapArgs ta{};
+  ta.cells = reinterpret_cast<const _Float16*>(s->cells); ta.wDb = s->fwDb; ta.bDb = s->bDb;
+  ta.sel = s->sel; ta.sel_count = s->sel_count; ta.sel_stride = kCandCap; ta.per_image = (k > 0 ? k : kCandCap);
+  ta.nms = s->scores; ta.features = d_features; ta.feat_cap = capacity; ta.counts = d_counts; ta.B = B; ta.H = H; ta.W = W;
+  return ta;
+}
 }  // namespace
 
 extern "C" int rspl_sp_infer_device(rspl_sp* s, const uint8_t* d_images, int B, int H, int W, int stride,
@@ -333,41 +375,21 @@ extern "C" int rspl_sp_infer_device(rspl_sp* s, const uint8_t* d_images, int B, 
     s->last_B = B; s->last_H = H; s->last_W = W;
     return RSPL_OK;
   } else if (s->cfg.precision == RSPL_PREC_FP16) {  // the reference's TensorRT kFP16 engine (super_point.cpp:98)
-    _Float16* hA = reinterpret_cast<_Float16*>(s->actA);
-    _Float16* hB = reinterpret_cast<_Float16*>(s->actB);
-    c.H = H; c.W = W; c.cout = 64; c.hw = s->hw1b; c.bias = s->b1b; c.hout = hA;
     // stage 0 = the fused conv1 kernel exactly (events stamped by the launch itself)
-    RSPL_HIP(conv3x3_h(c, 64, true, true, false, B, st, s->timer.slot(0), s->timer.slot(1)));  // conv1a+1b+pool
-    c.H = H2; c.W = W2; c.cout = 64; c.hin = hA; c.hw = s->hw2a; c.bias = s->b2a; c.hout = hB;
-    RSPL_HIP(conv3x3_h(c, 64, false, false, false, B, st));                   // conv2a
-    c.hin = hB; c.hw = s->hw2b; c.bias = s->b2b; c.hout = hA;
-    RSPL_HIP(conv3x3_h(c, 64, true, false, false, B, st));                    // conv2b+pool
-    c.H = H4; c.W = W4; c.cout = 128; c.hin = hA; c.hw = s->hw3a; c.bias = s->b3a; c.hout = hB;
-    RSPL_HIP(conv3x3_h(c, 64, false, false, false, B, st));                   // conv3a
-    c.hin = hB; c.hw = s->hw3b; c.bias = s->b3b; c.hout = hA;
-    RSPL_HIP(conv3x3_h(c, 128, true, false, false, B, st));                   // conv3b+pool
-    c.H = H8; c.W = W8; c.hin = hA; c.hw = s->hw4a; c.bias = s->b4a; c.hout = hB;
-    RSPL_HIP(conv3x3_h(c, 128, false, false, false, B, st));                  // conv4a
-    c.hin = hB; c.hw = s->hw4b; c.bias = s->b4b; c.hout = hA;
-    RSPL_HIP(conv3x3_h(c, 128, false, false, false, B, st));                  // conv4b
-    s->timer.mark(2, st);
-    c.cout = 512; c.hin = hA; c.hw = s->hwPD; c.bias = s->bPD; c.hout = reinterpret_cast<_Float16*>(s->cells);
-    RSPL_HIP(conv3x3_h(c, 128, false, false, false, B, st));                  // convPa | convDa (fp16 out)
+    const int lh[kH16Convs] = {H, H2, H2, H4, H4, H8, H8, H8}, lw[kH16Convs] = {W, W2, W2, W4, W4, W8, W8, W8};
+    for (int i = 0; i < kH16Convs; i++) {  // conv1a+1b+pool, conv2a .. conv4b, convPa | convDa (fp16 out)
+      RSPL_HIP(h16_conv(s, i, c, lh[i], lw[i], B, st, i ? nullptr : s->timer.slot(0), i ? nullptr : s->timer.slot(1)));
+      if (i == kH16Convs - 2) s->timer.mark(2, st);
+    }
     s->timer.mark(3, st);
     // detector head (superpoint.py:130-135) on fp16 MFMA
-    HeadHArgs h{};
-    h.cells = c.hout; h.wPb = s->fwPb; h.bPb = s->bPb; h.scores = s->scores; h.B = B; h.P = P; h.W8 = W8;
-    RSPL_HIP(det_head_h(h, false, st));
+    RSPL_HIP(det_head_h(h16_head(s, B, P, W8), false, st));
     s->timer.mark(4, st);
     if (int rc = nms_topk(s, B, H, W, k, st)) return rc;
     // descriptor head at the sampled taps + sampling + packing (superpoint.py:159-161,
     // super_point.cpp:206-319)
     s->timer.mark(6, st);
-    TapArgs ta{};
-    ta.cells = c.hout; ta.wDb = s->fwDb; ta.bDb = s->bDb;
-    ta.sel = s->sel; ta.sel_count = s->sel_count; ta.sel_stride = kCandCap; ta.per_image = (k > 0 ? k : kCandCap);
-    ta.nms = s->scores; ta.features = d_features; ta.feat_cap = capacity; ta.counts = d_counts; ta.B = B; ta.H = H; ta.W = W;
-    RSPL_HIP(sample_taps_h(ta, false, st));
+    RSPL_HIP(sample_taps_h(h16_taps(s, d_features, capacity, d_counts, B, H, W), false, st));
     s->timer.mark(7, st);
     s->timer.end_call();
     s->last_B = B; s->last_H = H; s->last_W = W;
@@ -504,5 +526,81 @@ extern "C" int rspl_sp_debug_nms(rspl_sp* s, const float* scores, int H, int W, 
   RSPL_HIP(hipMemcpyAsync(out, s->nms, sizeof(float) * H * W, hipMemcpyDeviceToHost, st));
   RSPL_HIP(hipStreamSynchronize(st));
   s->last_B = 0;
+  return RSPL_OK;
+}
+
+extern "C" int rspl_sp_debug_layer(rspl_sp* s, int stage, int B, int H, int W, const void* in, const float* scores,
+                                   const int32_t* kp, const int32_t* kp_counts, int kp_stride, void* out,
+                                   int32_t* counts_out) {
+  RSPL_CHECK_ARG(s && in && out, "rspl_sp_debug_layer: NULL argument");
+  RSPL_CHECK_ARG(s->cfg.precision == RSPL_PREC_FP16, "rspl_sp_debug_layer: the handle must be RSPL_PREC_FP16");
+  RSPL_CHECK_ARG(stage >= RSPL_SP_LAYER_CONV1 && stage <= RSPL_SP_LAYER_TAPS, "no such stage %d", stage);
+  RSPL_CHECK_ARG(B >= 1 && B <= s->cfg.max_batch && H > 0 && W > 0, "batch %d / level %dx%d out of range", B, H, W);
+  // arena capacities in halves (the fp32-sized buffers of carve())
+  const size_t mHW = (size_t)s->cfg.max_batch * s->cfg.max_height * s->cfg.max_width;
+  const size_t act_cap = mHW * 32, cell_cap = mHW / 64 * 1024;
+  hipStream_t st = s->stream;
+  RSPL_HIP(hipStreamSynchronize(st));
+  s->last_B = 0;  // the activations of the last inference are overwritten
+  auto up_half = [&](const float* src, _Float16* dst, size_t n) {
+    std::vector<_Float16> h(n);
+    for (size_t i = 0; i < n; i++) h[i] = (_Float16)src[i];
+    return hipMemcpy(dst, h.data(), n * sizeof(_Float16), hipMemcpyHostToDevice);
+  };
+  auto down_half = [&](const _Float16* src, float* dst, size_t n) {
+    std::vector<_Float16> h(n);
+    const hipError_t e = hipMemcpy(h.data(), src, n * sizeof(_Float16), hipMemcpyDeviceToHost);
+    for (size_t i = 0; i < n; i++) dst[i] = (float)h[i];
+    return e;
+  };
+  if (stage <= RSPL_SP_LAYER_CONVPD) {
+    const H16Conv d = h16_conv_desc(s, stage);
+    RSPL_CHECK_ARG(!d.pool || (H % 2 == 0 && W % 2 == 0), "a pooled stage needs even H, W");
+    const size_t n_in = (size_t)B * H * W * (stage ? d.cin : 1);
+    const size_t n_out = (size_t)B * (d.pool ? (H / 2) * (W / 2) : H * W) * d.cout;
+    RSPL_CHECK_ARG(n_out <= (stage == RSPL_SP_LAYER_CONVPD ? cell_cap : act_cap) && (stage ? n_in <= act_cap : n_in <= mHW),
+                   "level %dx%d x %d exceeds the handle's arena", H, W, B);
+    sp::ConvArgs c{};
+    if (stage == RSPL_SP_LAYER_CONV1) {
+      RSPL_HIP(hipMemcpy(s->image, in, n_in, hipMemcpyHostToDevice));
+      c.img = s->image; c.img_stride = W; c.img_pitch = (size_t)H * W; c.lut = s->lut; c.w1a = s->w1a; c.b1a = s->b1a;
+    } else {
+      RSPL_HIP(up_half(static_cast<const float*>(in), const_cast<_Float16*>(h16_conv_in(s, stage)), n_in));
+    }
+    RSPL_HIP(h16_conv(s, stage, c, H, W, B, st));
+    RSPL_HIP(hipStreamSynchronize(st));
+    RSPL_HIP(down_half(h16_conv_out(s, stage), static_cast<float*>(out), n_out));
+    return RSPL_OK;
+  }
+  // the heads: H x W is the cell grid
+  const int P = H * W;
+  RSPL_CHECK_ARG((size_t)B * P * 512 <= cell_cap && (size_t)B * P * 64 <= mHW, "cell grid %dx%d x %d exceeds the arena", H,
+                 W, B);
+  RSPL_HIP(up_half(static_cast<const float*>(in), reinterpret_cast<_Float16*>(s->cells), (size_t)B * P * 512));
+  if (stage == RSPL_SP_LAYER_DET_HEAD) {
+    RSPL_HIP(sp::det_head_h(h16_head(s, B, P, W), false, st));
+    RSPL_HIP(hipStreamSynchronize(st));
+    RSPL_HIP(hipMemcpy(out, s->scores, sizeof(float) * B * P * 64, hipMemcpyDeviceToHost));
+    return RSPL_OK;
+  }
+  RSPL_CHECK_ARG(scores && kp && kp_counts && counts_out && kp_stride >= 1, "taps: NULL argument");
+  const sp::TapArgs ta = h16_taps(s, s->features, s->feat_cap, s->counts, B, 8 * H, 8 * W);
+  for (int b = 0; b < B; b++) {
+    RSPL_CHECK_ARG(kp_counts[b] >= 0 && kp_counts[b] <= kp_stride && kp_counts[b] <= ta.per_image,
+                   "taps: count %d outside [0, %d]", kp_counts[b], std::min(kp_stride, ta.per_image));
+    for (int i = 0; i < kp_counts[b]; i++)
+      RSPL_CHECK_ARG(kp[(size_t)b * kp_stride + i] >= 0 && kp[(size_t)b * kp_stride + i] < P * 64,
+                     "taps: keypoint index outside the map");
+    if (kp_counts[b])
+      RSPL_HIP(hipMemcpy(s->sel + (size_t)b * kCandCap, kp + (size_t)b * kp_stride, sizeof(unsigned) * kp_counts[b],
+                         hipMemcpyHostToDevice));
+  }
+  RSPL_HIP(hipMemcpy(s->sel_count, kp_counts, sizeof(int) * B, hipMemcpyHostToDevice));
+  RSPL_HIP(hipMemcpy(s->scores, scores, sizeof(float) * B * P * 64, hipMemcpyHostToDevice));
+  RSPL_HIP(hipMemset(s->features, 0, sizeof(double) * B * s->feat_cap * 259));
+  RSPL_HIP(sp::sample_taps_h(ta, false, st));
+  RSPL_HIP(hipStreamSynchronize(st));
+  RSPL_HIP(hipMemcpy(out, s->features, sizeof(double) * B * s->feat_cap * 259, hipMemcpyDeviceToHost));
+  RSPL_HIP(hipMemcpy(counts_out, s->counts, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
   return RSPL_OK;
 }

@@ -4,7 +4,8 @@ in fp32 (an fp16 x fp16 product is exact in fp32, so this is the MFMA's arithmet
 order) and, when the NEXT layer is fp16 too, its output is stored rounded to fp16 -- exactly the roundings of
 librspl's fp16 kernels (sp_kernels.hip: conv3x3_h_kernel / conv1_res_kernel / det_head_h_kernel /
 sample_taps_h_kernel).  An fp32 layer is the parity path's arithmetic.  The post-processing (NMS, threshold,
-borders, top-k, fp64 sampling) is the oracle's (oracle/post.py), i.e. the reference's.
+borders, top-k, fp64 sampling) is the oracle's (oracle/post.py), i.e. the reference's.  The emulation itself
+is oracle/fp16_emu.py's Emu.
 
 For each split it reports, over the C1 images (tools/run_c1_plumbing.py's synthetic.stereo_pair seeds
 300..), the keypoint-set overlap with the fp32 oracle per image (mean / min), the fraction of identical sets,
@@ -20,7 +21,6 @@ import sys
 
 import numpy as np
 import torch
-import torch.nn.functional as Fn
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
@@ -31,9 +31,9 @@ pkg = rspl_loader.load()
 import oracle  # noqa: E402
 import post  # noqa: E402
 
+from fp16_emu import ENC, HEADS, Emu  # noqa: E402  (the layer emulation, shared with the tests)
+
 H, W, K = 480, 752, 400
-ENC = ["conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b"]
-HEADS = ["convPa", "convPb", "convDa", "convDb"]
 SPLITS = {
     "fp16_all": set(ENC + HEADS),                       # the product's fp16 path today
     "fp32_all": set(),
@@ -48,72 +48,6 @@ SPLITS = {
     "x2w_all": {n: "x2w" for n in ENC + HEADS},           # weights split only
     "x3_enc16c1": {**{n: "x3" for n in ENC[2:] + HEADS}, "conv1a": "16", "conv1b": "16"},  # conv1 fp16, rest split
 }
-
-
-def r16(t):
-    return t.half().float()
-
-
-def split16(t):
-    """t = hi + lo, both fp16 (lo unscaled: it goes subnormal below |t| ~ 0.125, where its absolute error
-    stays under fp16's subnormal spacing of 6e-8)"""
-    hi = r16(t)
-    return hi, r16(t - hi)
-
-
-class Emu:
-    """Per layer one of: "16" (fp16 operands, fp32 accumulation), "x3" (split fp16: activations and weights as
-    hi + lo fp16 pairs, three MFMA products hi*hi + lo*hi + hi*lo accumulated in fp32), "x2a" / "x2w" (only the
-    activations / only the weights split: two products), anything else fp32.  A layer's output is stored fp16
-    only when the next layer is "16" (x2w too reads fp16 activations); otherwise it stays fp32 (x3 / x2a split
-    it at load)."""
-    def __init__(self, blob):
-        self.w = {k: torch.from_numpy(np.asarray(v, np.float32)) for k, v in pkg.weights.read_blob(blob).items()}
-
-    def conv(self, x, name, mode, out16, relu=True, pad=1):
-        w, b = self.w[name + ".weight"], self.w[name + ".bias"]
-        if mode in ("16", "x2w"):
-            x = r16(x)
-        if mode == "16" and name == "conv1a":  # conv1_res_kernel: the bias rides the MFMA as the tenth tap (fp16)
-            b = r16(b)
-        if mode == "16":
-            y = Fn.conv2d(x, r16(w), b, padding=pad)
-        elif mode in ("x3", "x2a", "x2w"):
-            xh, xl = split16(x)
-            wh, wl = split16(w)
-            y = Fn.conv2d(xh, wh, b, padding=pad)
-            if mode in ("x3", "x2a"):
-                y = y + Fn.conv2d(xl, wh, None, padding=pad)
-            if mode in ("x3", "x2w"):
-                y = y + Fn.conv2d(xh, wl, None, padding=pad)
-        else:
-            y = Fn.conv2d(x, w, b, padding=pad)
-        if relu:
-            y = Fn.relu(y)
-        return r16(y) if out16 else y
-
-    def forward(self, img_u8, half):
-        """half: a set of fp16 layers, or a dict layer -> mode"""
-        md = half if isinstance(half, dict) else {n: "16" for n in half}
-        m = lambda n: md.get(n, "32")  # noqa: E731
-        o16 = lambda n: m(n) in ("16", "x2w")  # noqa: E731  (the layer reads fp16 activations)
-        x = torch.from_numpy(post.image_to_input(img_u8))[None, None]
-        seq = ENC + ["convPa"]
-        for i, name in enumerate(ENC):
-            nxt = seq[i + 1]
-            x = self.conv(x, name, m(name), m(name) != "32" and o16(nxt))
-            if name in ("conv1b", "conv2b", "conv3b"):
-                x = Fn.max_pool2d(x, 2, 2)
-        pa = self.conv(x, "convPa", m("convPa"), m("convPa") != "32" and o16("convPb"))
-        da = self.conv(x, "convDa", m("convDa"), m("convDa") != "32" and o16("convDb"))
-        semi = self.conv(pa, "convPb", m("convPb"), False, relu=False, pad=0)
-        desc = self.conv(da, "convDb", m("convDb"), False, relu=False, pad=0)
-        s = torch.softmax(semi, 1)[:, :-1]
-        h8, w8 = s.shape[2], s.shape[3]
-        s = s.permute(0, 2, 3, 1).reshape(1, h8, w8, 8, 8).permute(0, 1, 3, 2, 4).reshape(h8 * 8, w8 * 8)
-        desc = Fn.normalize(desc, p=2, dim=1)[0]
-        scores = oracle.simple_nms(s.numpy().astype(np.float32))
-        return post.sp_postprocess(scores, desc.numpy(), 0.004, 4, K)
 
 
 def keys(F):
@@ -145,7 +79,7 @@ def main():
     oracle.set_threads(a.threads)
     sp_w, _ = pkg.weights.ensure_blobs(str(ROOT / "weights"))
     sg_w = pkg.weights.ensure_sg_profile_blob(str(ROOT / "weights"), "c1")
-    emu = Emu(sp_w)
+    emu = Emu(sp_w, K)
     names = a.splits.split(",")
     stats = {n: {"overlap": [], "cos": [], "agree": [], "agree_th": []} for n in names}
     for t in range(a.pairs):
