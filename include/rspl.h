@@ -238,6 +238,19 @@ int rspl_sg_debug_decode(rspl_sg* sg, const float* Z, int n0, int n1, int32_t* i
 int rspl_sg_debug_layers(rspl_sg* sg, int batch, float* X, const int32_t* n0, const int32_t* n1, int l0, int l1,
                          uint16_t* Q);
 
+/* Test hook: the Sinkhorn kernel that rspl_sg_create chooses for a handle of (max_keypoints, max_batch) on a
+ * device of cu_count CUs, under the RSPL_SG_SINK / RSPL_SG_SINK_G overrides as create reads them.  No device is
+ * touched, except that cu_count 0 stands for the current device's CU count.
+ * kind: 0 slab kernel, 1 slab kernel reading its slabs from global memory, 2 scaling form (nmax + 1 <= 448),
+ * 3 scaling form (<= 640), 4 wide scaling form (<= 2112); groups: workgroups per pair; rows_per_wave: of the scaling
+ * forms (0 for the slab kernel); ug / vg_granules: 8-byte exchange granules of the whole handle.  RSPL_E_ARG
+ * where rspl_sg_create would refuse max_batch. */
+typedef struct {
+  int32_t kind, groups, rows_per_wave, reserved;
+  uint64_t ug_granules, vg_granules;
+} rspl_sg_sinkhorn_plan;
+int rspl_sg_debug_sinkhorn_plan(int max_keypoints, int max_batch, int cu_count, rspl_sg_sinkhorn_plan* out);
+
 /* Stages: 0 prep + keypoint encoder, 1 18 GNN layers, 2 final_proj + scores + bins,
  * 3 hand-over to the post stream (queueing behind the previous call's post work; no kernel),
  * 4 log-Sinkhorn (one kernel), 5 decode. */

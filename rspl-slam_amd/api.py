@@ -157,6 +157,20 @@ class SuperGlueConfig:                # include/read_configs.h:20-28 (+ arena si
     device: int = 0
 
 
+SINK_KINDS = ("slab", "slab_scratch", "sc", "sc10", "wide")  # rspl_sg_sinkhorn_plan.kind
+
+
+def sinkhorn_plan(max_keypoints: int, max_batch: int = 1, cu_count: int = 0):
+    """rspl_sg_debug_sinkhorn_plan: the Sinkhorn kernel a handle of this size gets on cu_count CUs (0: the current
+    device's; any other value touches no device), under RSPL_SG_SINK / RSPL_SG_SINK_G.  Returns None where
+    rspl_sg_create would refuse max_batch, else a dict (kind: one of SINK_KINDS)."""
+    pl = capi.SgSinkhornPlan()
+    if capi.load().rspl_sg_debug_sinkhorn_plan(max_keypoints, max_batch, cu_count, C.byref(pl)) != 0:
+        return None
+    return dict(kind=SINK_KINDS[pl.kind], groups=pl.groups, rows_per_wave=pl.rows_per_wave,
+                ug_granules=pl.ug_granules, vg_granules=pl.vg_granules)
+
+
 class SuperGlue:
     """Mirror of class SuperGlue (include/super_glue.h:20-71)."""
 

@@ -35,6 +35,7 @@ EXPORTS = [
     "rspl_sp_stage_times", "rspl_sp_destroy",
     "rspl_sg_create", "rspl_sg_infer", "rspl_sg_infer_device", "rspl_sg_infer_device2", "rspl_sg_debug_scores", "rspl_sg_profile",
     "rspl_sg_status", "rspl_sg_debug_inject", "rspl_sg_debug_sinkhorn", "rspl_sg_debug_decode", "rspl_sg_debug_layers",
+    "rspl_sg_debug_sinkhorn_plan",
     "rspl_sg_stage_times", "rspl_sg_destroy",
     "rspl_pm_match",
     "rspl_ba_create", "rspl_ba_local", "rspl_ba_submit", "rspl_ba_join", "rspl_ba_destroy", "rspl_ba_use_reserved_cus", "rspl_ba_kernel_timing",
@@ -61,6 +62,11 @@ class SgConfig(C.Structure):
     _fields_ = [("image_width", C.c_int), ("image_height", C.c_int), ("max_keypoints", C.c_int),
                 ("max_batch", C.c_int), ("sinkhorn_iterations", C.c_int), ("precision", C.c_int),
                 ("device", C.c_int)]
+
+
+class SgSinkhornPlan(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("groups", C.c_int32), ("rows_per_wave", C.c_int32), ("reserved", C.c_int32),
+                ("ug_granules", C.c_uint64), ("vg_granules", C.c_uint64)]
 
 
 class DMatch(C.Structure):
@@ -184,6 +190,7 @@ def load(path: pathlib.Path = LIB_PATH):
         lib.rspl_sg_debug_sinkhorn.argtypes = [vp, vp, ip, ip, C.c_float, ip, vp]
         lib.rspl_sg_debug_decode.argtypes = [vp, vp, ip, ip, vp, vp, vp, vp]
         lib.rspl_sg_debug_layers.argtypes = [vp, ip, vp, vp, vp, ip, ip, vp]
+        lib.rspl_sg_debug_sinkhorn_plan.argtypes = [ip, ip, ip, C.POINTER(SgSinkhornPlan)]
         lib.rspl_sg_profile.argtypes = [vp, ip]
         lib.rspl_sg_stage_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(ip)]
         lib.rspl_sg_destroy.argtypes = [vp]

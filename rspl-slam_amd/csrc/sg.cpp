@@ -1,4 +1,4 @@
-// SuperGlue + PointMatching handle: C ABI (include/rspl.h) over sg_kernels.hip.
+// SuperGlue + PointMatching handle: C ABI (include/rspl.h) over sg_gemm.hip, sg_gnn.hip and sg_sinkhorn.hip.
 // Mirrors SuperGlue::build / infer / process_output (src/super_glue.cpp:21-472) and
 // PointMatching::MatchingPoints (src/point_matching.cc:12-62).
 #include <algorithm>
@@ -23,7 +23,7 @@ struct rspl_sg {
   rspl_sg_config cfg{};
   hipStream_t stream = nullptr;
   Arena arena;
-  int nmax = 0, B = 0, G = 0, ld = 0;
+  int nmax = 0, B = 0, ld = 0;
   // weights
   float* kw[5];
   float* kb[5];
@@ -33,20 +33,16 @@ struct rspl_sg {
   float *wf, *bf, *bin;
   // RSPL_PREC_FP16: transposed fp16 copies [N][K] of every projection / MLP weight
   _Float16* hkw[5];
-  _Float16 *hwqkv, *hwm, *hw1, *hw2, *hwf;
+  _Float16 *hwqkv, *hw1, *hw2, *hwf;
   _Float16 *fwqkv, *fw1, *fw2;  // the same in MFMA B-fragment order (fused GNN layers)
   // activations
   float *kin, *h1, *h2, *X, *QKV, *O, *MSG, *HID, *cpl, *Z, *val0;
-  // RSPL_PREC_FP16 GNN activations: fp16 shadow of X, Q | K, V^T per head, messages, hidden
-  _Float16 *Xh, *QKh, *Vth, *Oh, *MSGh, *HIDh;
+  _Float16* Xh;  // RSPL_PREC_FP16: fp16 shadow of X
   _Float16 *Qf[2], *Kf[2], *Vf[2];  // fused layers: q (row-major) / k, v (MFMA fragment order), ping-pong
-  int ldv = 0;  // token stride of Vth (nmax rounded up to the 32-key attention tile; zero padded)
-  unsigned long long *ug, *vg;  // Sinkhorn u / v exchange granules [B][ld] (row-block: ug = [B][2][rbG][ld])
-  int rbG = 0;                  // row-block Sinkhorn workgroups per pair (0: slab kernel)
-  bool sink_sc = false;         // with rbG: the scaling-form kernel
-  bool sink_wide = false;       // with sink_sc: the wide two-hop kernel (640 < nmax + 1 <= 2112)
-  float* cplT = nullptr;        // transposed column slabs when they exceed LDS [B][ld*ld]
-  bool sink_scratch = false;
+  int ldv = 0;  // tokens per set in Kf / Vf (nmax rounded up to the 32-key attention tile; zero padded)
+  sg::SinkPlan sink{};          // the Sinkhorn kernel, its workgroups per pair and exchange buffer sizes
+  unsigned long long *ug, *vg;  // Sinkhorn exchange granules (sink.ug_granules, sink.vg_granules)
+  float* cplT = nullptr;        // SinkKind::SlabScratch: transposed column slabs [B][ld*ld]
   unsigned* err = nullptr;      // [B] sticky Sinkhorn timeout flags, host-mapped (rspl_sg_status)
   unsigned* d_err = nullptr;    // device alias of err
   unsigned sk_seq = 0;
@@ -73,16 +69,6 @@ struct rspl_sg {
 
 namespace {
 
-// Sinkhorn exchange granules: ug = [B][ld] (slab), [B][2][rbG][ld] (row-block / scaling form) or the wide
-// kernel's hop-1 buffers [B][2][G][G][cs]; vg = [B][ld] or the wide kernel's hop-2 buffers [B][2][G cs]
-size_t ug_len(const rspl_sg* s) {
-  if (s->sink_wide) return (size_t)s->B * sg::sinkhorn_wide_hop1_len(s->nmax);
-  return (size_t)s->B * s->ld * (s->rbG ? 2 * s->rbG : 1);
-}
-size_t vg_len(const rspl_sg* s) {
-  return s->sink_wide ? (size_t)s->B * sg::sinkhorn_wide_hop2_len(s->nmax) : (size_t)s->B * s->ld;
-}
-
 template <typename F>
 void carve(F& ar, rspl_sg* s) {
   const size_t T = (size_t)s->B * 2 * s->nmax, ld = s->ld, B = s->B;
@@ -103,20 +89,20 @@ void carve(F& ar, rspl_sg* s) {
   take(s->w2, (size_t)kLayers * 512 * 256); take(s->b2, (size_t)kLayers * 256);
   take(s->wf, 256 * 256); take(s->bf, 256); take(s->bin, 4);
   for (int i = 0; i < 5; i++) take(s->hkw[i], (size_t)(i == 0 ? kKencIn : kKencCh[i]) * kKencCh[i + 1]);
-  take(s->hwqkv, (size_t)kLayers * 256 * 768); take(s->hwm, (size_t)kLayers * 256 * 256);
+  take(s->hwqkv, (size_t)kLayers * 256 * 768);
   take(s->hw1, (size_t)kLayers * 512 * 512); take(s->hw2, (size_t)kLayers * 512 * 256); take(s->hwf, 256 * 256);
   take(s->fwqkv, (size_t)kLayers * 256 * 768); take(s->fw1, (size_t)kLayers * 512 * 512);
   take(s->fw2, (size_t)kLayers * 512 * 256);
   take(s->kin, T * kKencIn); take(s->h1, T * 256); take(s->h2, T * 256);
   take(s->X, T * 256); take(s->QKV, T * 768); take(s->O, T * 256); take(s->MSG, T * 256); take(s->HID, T * 512);
-  take(s->Xh, T * 256); take(s->QKh, T * 512); take(s->Vth, (size_t)B * 2 * 256 * s->ldv); take(s->Oh, T * 256);
-  take(s->MSGh, T * 256); take(s->HIDh, T * 512);
+  take(s->Xh, T * 256);
   for (int i = 0; i < 2; i++) {
     take(s->Qf[i], T * 256); take(s->Kf[i], (size_t)B * 2 * 256 * s->ldv); take(s->Vf[i], (size_t)B * 2 * 256 * s->ldv);
   }
 
-  take(s->cpl, 2 * B * ld * ld); take(s->Z, 2 * B * ld * ld); take(s->ug, ug_len(s)); take(s->vg, vg_len(s));
-  if (s->sink_scratch) take(s->cplT, B * ld * ld);
+  take(s->cpl, 2 * B * ld * ld); take(s->Z, 2 * B * ld * ld); take(s->ug, s->sink.ug_granules);
+  take(s->vg, s->sink.vg_granules);
+  if (s->sink.kind == sg::SinkKind::SlabScratch) take(s->cplT, B * ld * ld);
   take(s->dbg_alpha, 4);
   take(s->cn0, 2 * B); take(s->cn1, 2 * B);
   take(s->max0, B * s->nmax); take(s->val0, B * s->nmax); take(s->max1, B * s->nmax);
@@ -295,19 +281,27 @@ static int run_gnn_h(rspl_sg* s, int B, int l0, int l1, const int* d_n0, const i
   return RSPL_OK;
 }
 
+// sg::sinkhorn_plan under the RSPL_SG_SINK / RSPL_SG_SINK_G overrides (rspl_sg_create, rspl_sg_debug_sinkhorn_plan)
+static int plan_sinkhorn(int nmax, int B, int ncu, sg::SinkPlan* out) {
+  const char* g = getenv("RSPL_SG_SINK_G");
+  if (!sg::sinkhorn_plan(nmax, B, ncu, getenv("RSPL_SG_SINK"), g ? std::max(1, atoi(g)) : 0, out)) {
+    set_error("max_batch (%d) exceeds the CU count (%d): the Sinkhorn workgroups must be co-resident", B, ncu);
+    return RSPL_E_ARG;
+  }
+  return RSPL_OK;
+}
+
 // log_optimal_transport (superglue.py:185-205) on the couplings of B pairs, on stream st
 static hipError_t run_sinkhorn(rspl_sg* s, const float* cpl, float* Zp, const int* cn0, const int* cn1, int B,
                                int iters, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
-  hipError_t e;
   sg::SinkArgs sk{};
   sk.cpl = cpl; sk.Z = Zp; sk.cplT = s->cplT; sk.ug = s->ug; sk.vg = s->vg;
   sk.seq = s->sk_seq = (s->sk_seq % 0xFFFFFu) + 1;
   sk.spin_limit = s->spin_limit; sk.inject = s->inject;
   sk.err = s->d_err; sk.n0 = cn0; sk.n1 = cn1;
-  sk.nmax = s->nmax; sk.G = s->rbG ? s->rbG : s->G; sk.rb = s->rbG > 0; sk.sc = s->sink_sc; sk.iters = iters;
-  sk.wide = s->sink_wide;
+  sk.nmax = s->nmax; sk.iters = iters;
   sk.sleep = 1;
-  return sg::sinkhorn(sk, B, st, t0, t1);
+  return sg::sinkhorn(sk, s->sink, B, st, t0, t1);
 }
 
 extern "C" int rspl_sg_create(const rspl_sg_config* cfg, const char* weights_path, rspl_sg** out) {
@@ -331,64 +325,24 @@ extern "C" int rspl_sg_create(const rspl_sg_config* cfg, const char* weights_pat
   s->nmax = cfg->max_keypoints;  // output stride per pair (rspl.h)
   s->ld = s->nmax + 1;
   s->ldv = (s->nmax + 31) / 32 * 32;
-  {  // Sinkhorn workgroups per pair: ~kRows rows + columns each, and at least enough that both
-     // slabs fit one workgroup's LDS; all B*G workgroups must be co-resident (one per CU)
+  {  // the Sinkhorn kernel and its workgroups per pair: all of them must be co-resident (one per CU)
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess || ncu < 1) {
       set_error("hipDeviceGetAttribute(MultiprocessorCount) failed");
       delete s;
       return RSPL_E_DEVICE;
     }
-    constexpr int kRows = 9;  // 45 workgroups per pair at N = 400 (round-2 A/B: 32 vs 48)
-    int G = std::max(1, (s->ld + kRows - 1) / kRows);
-    while (G < s->ld && sg::sinkhorn_lds_bytes(s->nmax, G, true) > sg::kSinkLdsMax) G++;
-    if (const char* e = getenv("RSPL_SG_SINK_G"); e && getenv("RSPL_SG_SINK") &&
-        std::string(getenv("RSPL_SG_SINK")) == "slab")
-      G = std::max(1, atoi(e));
-    G = std::min(G, std::max(1, ncu / s->B));
-    s->G = G;
-    s->sink_scratch = sg::sinkhorn_lds_bytes(s->nmax, G, true) > sg::kSinkLdsMax;
-    // nmax + 1 <= 640: rows in registers, one exchange per iteration -- the scaling-form kernel (8 workgroups
-    // per pair); RSPL_SG_SINK=slab keeps the slab kernel; RSPL_SG_SINK_G sets the workgroups per pair
-    const char* sk = getenv("RSPL_SG_SINK");
-    const std::string kind = sk ? sk : "sc";
-    if (kind != "slab") {
-      int rg = 8;
-      if (const char* e = getenv("RSPL_SG_SINK_G")) rg = std::max(1, atoi(e));
-      s->sink_sc = true;
-      rg = std::min(rg, std::max(1, ncu / s->B));
-      while (rg <= 32 && rg * s->B <= ncu && !sg::sinkhorn_rb_rpw(s->nmax, rg)) rg++;
-      if (rg * s->B <= ncu && sg::sinkhorn_rb_rpw(s->nmax, rg)) s->rbG = rg;
-      // 448 < nmax + 1 <= 640 (e.g. C4's 600 keypoints): the scaling-form kernel with ten column
-      // sets per lane, ceil(ld / 48) workgroups of <= 48 rows per pair
-      if (!s->rbG && s->sink_sc) {
-        int g = (s->ld + 47) / 48;
-        if (const char* e = getenv("RSPL_SG_SINK_G")) g = std::max(1, atoi(e));
-        if (g * s->B <= ncu && sg::sinkhorn_sc10_ok(s->nmax, g)) s->rbG = g;
-      }
-      // 640 < nmax + 1 <= 2112 (C5's 2048 keypoints): the wide scaling-form kernel, 32 rows per workgroup,
-      // the column exchange in two hops (reduce-scatter to the column owners, broadcast of V)
-      if (!s->rbG && s->sink_sc) {
-        const int g = sg::sinkhorn_wide_groups(s->nmax);
-        if (g * s->B <= ncu && sg::sinkhorn_wide_ok(s->nmax, g)) {
-          s->rbG = g;
-          s->sink_wide = true;
-        }
-      }
-    }
-    if (s->B * s->G > ncu && !s->rbG) {
-      set_error("max_batch (%d) exceeds the CU count (%d): the Sinkhorn workgroups must be co-resident", s->B, ncu);
+    if (int prc = plan_sinkhorn(s->nmax, s->B, ncu, &s->sink)) {
       delete s;
-      return RSPL_E_ARG;
+      return prc;
     }
   }
   Sizer sz;
   carve(sz, s);
   if ((rc = s->arena.reserve(sz.used))) { delete s; return rc; }
   carve(s->arena, s);
-  if (hipMemset(s->ug, 0, sizeof(unsigned long long) * ug_len(s)) != hipSuccess ||
-      hipMemset(s->vg, 0, sizeof(unsigned long long) * vg_len(s)) != hipSuccess ||
-      hipMemset(s->Vth, 0, sizeof(_Float16) * s->B * 2 * 256 * s->ldv) != hipSuccess ||
+  if (hipMemset(s->ug, 0, sizeof(unsigned long long) * s->sink.ug_granules) != hipSuccess ||
+      hipMemset(s->vg, 0, sizeof(unsigned long long) * s->sink.vg_granules) != hipSuccess ||
       hipMemset(s->Kf[0], 0, sizeof(_Float16) * s->B * 2 * 256 * s->ldv) != hipSuccess ||
       hipMemset(s->Kf[1], 0, sizeof(_Float16) * s->B * 2 * 256 * s->ldv) != hipSuccess ||
       hipMemset(s->Vf[0], 0, sizeof(_Float16) * s->B * 2 * 256 * s->ldv) != hipSuccess ||
@@ -421,7 +375,6 @@ extern "C" int rspl_sg_create(const rspl_sg_config* cfg, const char* weights_pat
     for (int l = 0; l < kLayers; l++) {
       okh &= sg::to_half_t(s->wqkv + (size_t)l * 256 * 768, 256, 768, s->hwqkv + (size_t)l * 256 * 768, s->stream) ==
              hipSuccess;
-      okh &= sg::to_half_t(s->wm + (size_t)l * 65536, 256, 256, s->hwm + (size_t)l * 65536, s->stream) == hipSuccess;
       okh &= sg::to_half_t(s->w1m + (size_t)l * 512 * 512, 512, 512, s->hw1 + (size_t)l * 512 * 512, s->stream) ==
              hipSuccess;
       okh &= sg::to_half_t(s->w2 + (size_t)l * 512 * 256, 512, 256, s->hw2 + (size_t)l * 512 * 256, s->stream) ==
@@ -513,27 +466,27 @@ extern "C" int rspl_sg_infer_device2(rspl_sg* s, int B, const double* d_feat0, c
   // AttentionalGNN (superglue.py:165-173): ['self', 'cross'] * 9; both images read pre-layer descs
   if (h16) {  // fp16 activations end to end (X itself stays fp32: the residual stream)
     RSPL_HIP(sg::to_half(s->X, s->Xh, (size_t)T * 256, st));
-    // one launch per layer on one workgroup per 32-token tile (layer_kernel).  (Four launches per layer --
-    // QKV GEMM, attention, mlp.0, mlp.3 -- were slower and were removed in round 6; round 5 measured the layer on
-    // four workgroups per tile -- the same bits, slower in the pipeline: profiles/r05_experiments.md.)
-    // layer 0's q / k / v (prologue launch), then one fused launch per layer
+    // layer 0's q / k / v (prologue launch), then one fused launch per layer on one workgroup per 32-token tile
+    // (layer_kernel; round 5 measured the layer on four workgroups per tile -- the same bits, slower in the
+    // pipeline: profiles/r05_experiments.md)
     if (int rc = run_gnn_h(s, B, 0, kLayers, d_n0, d_n1, st)) return rc;
-  }
-  for (int l = 0; l < kLayers && !h16; l++) {
-    RSPL_HIP(sg::gemm(G_(s->X, 256, s->wqkv + (size_t)l * 256 * 768, 768, s->bqkv + (size_t)l * 768, s->QKV, 768, T,
-                         768, 256, 0, h16 ? s->hwqkv + (size_t)l * 256 * 768 : nullptr), 1, st));
-    sg::AttnArgs at{};
-    at.qkv = s->QKV; at.O = s->O; at.n0 = d_n0; at.n1 = d_n1; at.nmax = nm; at.cross = l & 1;
-    RSPL_HIP(sg::attention(at, B, st));
-    RSPL_HIP(sg::gemm(G_(s->O, 256, s->wm + (size_t)l * 65536, 256, s->bm + (size_t)l * 256, s->MSG, 256, T, 256, 256,
-                         0, h16 ? s->hwm + (size_t)l * 65536 : nullptr), 1, st));
-    sg::GemmArgs g1 = G_(s->X, 256, s->w1 + (size_t)l * 512 * 512, 512, s->b1 + (size_t)l * 512, s->HID, 512, T, 512,
-                         512, 1, h16 ? s->hw1 + (size_t)l * 512 * 512 : nullptr);
-    g1.A2 = s->MSG;  // torch.cat([x, message], dim=1)
-    g1.ksplit = 256;
-    RSPL_HIP(sg::gemm(g1, 1, st));
-    RSPL_HIP(sg::gemm(G_(s->HID, 512, s->w2 + (size_t)l * 512 * 256, 256, s->b2 + (size_t)l * 256, s->X, 256, T, 256,
-                         512, 2, h16 ? s->hw2 + (size_t)l * 512 * 256 : nullptr), 1, st));
+  } else {
+    for (int l = 0; l < kLayers; l++) {
+      RSPL_HIP(sg::gemm(G_(s->X, 256, s->wqkv + (size_t)l * 256 * 768, 768, s->bqkv + (size_t)l * 768, s->QKV, 768, T,
+                           768, 256, 0), 1, st));
+      sg::AttnArgs at{};
+      at.qkv = s->QKV; at.O = s->O; at.n0 = d_n0; at.n1 = d_n1; at.nmax = nm; at.cross = l & 1;
+      RSPL_HIP(sg::attention(at, B, st));
+      RSPL_HIP(sg::gemm(G_(s->O, 256, s->wm + (size_t)l * 65536, 256, s->bm + (size_t)l * 256, s->MSG, 256, T, 256,
+                           256, 0), 1, st));
+      sg::GemmArgs g1 = G_(s->X, 256, s->w1 + (size_t)l * 512 * 512, 512, s->b1 + (size_t)l * 512, s->HID, 512, T, 512,
+                           512, 1);
+      g1.A2 = s->MSG;  // torch.cat([x, message], dim=1)
+      g1.ksplit = 256;
+      RSPL_HIP(sg::gemm(g1, 1, st));
+      RSPL_HIP(sg::gemm(G_(s->HID, 512, s->w2 + (size_t)l * 512 * 256, 256, s->b2 + (size_t)l * 256, s->X, 256, T, 256,
+                           512, 2), 1, st));
+    }
   }
   s->timer.mark(2, st);
   // final_proj + scores / descriptor_dim**.5 (superglue.py:295-300)
@@ -542,7 +495,7 @@ extern "C" int rspl_sg_infer_device2(rspl_sg* s, int B, const double* d_feat0, c
     sg::GemmHArgs g{};
     g.A = s->Xh; g.lda = 256; g.ksplit = 256; g.B = s->hwf; g.ldb = 256; g.bias = s->bf; g.M = T; g.N = 256; g.K = 256;
     g.C32 = MD; g.ldc32 = 256;
-    RSPL_HIP(sg::gemm_h(g, 0, st));
+    RSPL_HIP(sg::gemm_h(g, st));
   } else {
     RSPL_HIP(sg::gemm(G_(s->X, 256, s->wf, 256, s->bf, MD, 256, T, 256, 256, 0, nullptr), 1, st));
   }
@@ -790,5 +743,20 @@ extern "C" int rspl_sg_debug_layers(rspl_sg* s, int B, float* X, const int32_t* 
     RSPL_HIP(hipMemcpyAsync(Q, s->Qf[l1 & 1], sizeof(uint16_t) * (size_t)B * 2 * s->nmax * 256, hipMemcpyDeviceToHost, st));
   RSPL_HIP(hipStreamSynchronize(st));
   s->last_B = 0;  // the debug call reused the batch's buffers
+  return RSPL_OK;
+}
+
+extern "C" int rspl_sg_debug_sinkhorn_plan(int max_keypoints, int max_batch, int cu_count, rspl_sg_sinkhorn_plan* out) {
+  RSPL_CHECK_ARG(out, "rspl_sg_debug_sinkhorn_plan: NULL argument");
+  RSPL_CHECK_ARG(max_keypoints > 0 && max_keypoints <= 4096, "max_keypoints must be in [1, 4096]");
+  RSPL_CHECK_ARG(cu_count >= 0, "cu_count must be >= 0");
+  if (!cu_count) {  // the current device's
+    int dev = 0;
+    RSPL_HIP(hipGetDevice(&dev));
+    RSPL_HIP(hipDeviceGetAttribute(&cu_count, hipDeviceAttributeMultiprocessorCount, dev));
+  }
+  sg::SinkPlan pl{};
+  if (int rc = plan_sinkhorn(max_keypoints, std::max(1, max_batch), cu_count, &pl)) return rc;
+  *out = rspl_sg_sinkhorn_plan{(int32_t)pl.kind, pl.G, pl.rpw, 0, pl.ug_granules, pl.vg_granules};
   return RSPL_OK;
 }

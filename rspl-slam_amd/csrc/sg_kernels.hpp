@@ -1,6 +1,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 namespace rspl {
@@ -31,13 +32,8 @@ struct GemmArgs {
   int count_stride;  // ints between consecutive batches in mcount/ncount
 };
 
-// fp16 GNN GEMM (RSPL_PREC_FP16): C = epi(A B^T + bias), A [M][K] fp16 (columns [ksplit, K)
-// from A2), B [N][K] fp16 (the transposed weights), K <= 512 and a multiple of 16.
-//   mode 0: C32 = v          1: C16 = v          2: C16 = relu(v)
-//        3: C32 += v, C16 = fp16(C32)  (the residual stream and its fp16 shadow)
-//        4: QKV: channels [0, 512) -> C16 (Q | K, row stride ldc16); [512, 768) (V) ->
-//           Vt[set][head][dim][token] (token = m % nmax, row stride ldv), so attention can
-//           feed V^T to the MFMA straight from memory
+// fp16 GEMM (RSPL_PREC_FP16, final_proj): C32 = A B^T + bias, A [M][K] fp16 (columns [ksplit, K)
+// from A2 when set), B [N][K] fp16 (the transposed weights), K <= 512 and a multiple of 64.
 struct GemmHArgs {
   const _Float16* A;
   const _Float16* A2;
@@ -48,10 +44,6 @@ struct GemmHArgs {
   int M, N, K;
   float* C32;
   int ldc32;
-  _Float16* C16;
-  int ldc16;
-  _Float16* Vt;
-  int nmax, ldv;
 };
 
 
@@ -117,20 +109,40 @@ struct SinkArgs {
   const float* cpl;   // couplings [B][ld*ld]
   float* Z;           // [B][ld*ld]
   float* cplT;        // [B][ld*ld] transposed column slabs (scratch; only when the slabs exceed LDS)
-  unsigned long long* ug;  // [B][ld] tagged u granules {f32 bits, tag}; row-block layout: [B][2][G][ld] partial sums
-  unsigned long long* vg;  // [B][ld] tagged v granules
+  unsigned long long* ug;  // [B][ld] tagged u granules {f32 bits, tag}; scaling form: [B][2][G][ld] partial sums;
+                           // wide kernel: its hop-1 buffers (SinkPlan::ug_granules in all)
+  unsigned long long* vg;  // [B][ld] tagged v granules; wide kernel: its hop-2 buffers
   unsigned seq;       // per-call tag base (never 0; granules start zeroed)
   unsigned spin_limit;  // bounded polls per granule before the exchange is declared timed out
   int inject;         // debug: workgroup 0 of pair 0 reports a timeout at iteration 0
   unsigned* err;      // [B] sticky timeout flags (host-mapped)
   const int* n0;
   const int* n1;
-  int nmax, G, iters;
-  int rb;             // 1: row-block layout (rows in registers, one exchange per iteration; with sc)
-  int sleep;          // row-block layout: s_sleep(1) units between re-polls (run_sinkhorn: 1)
-  int sc;             // with rb: the scaling-form kernel (register-resident exp(C + a + b), two mat-vecs per iteration)
-  int wide;           // with sc: the wide two-hop kernel (640 < nmax + 1 <= 2112; ug / vg laid out as its hop buffers)
+  // nmax, iters and sleep keep the kernarg offsets they were tuned at (80, 88, 96 of 112 bytes): packed, the
+  // scaling-form kernels load and schedule differently and the Sinkhorn stage measured 1.4 % slower at C3.  The
+  // reserved words are never read.
+  int nmax, reserved0, iters, reserved1;
+  int sleep;          // scaling-form kernels: s_sleep(1) units between re-polls (run_sinkhorn: 1)
+  int reserved2[2];
 };
+static_assert(sizeof(SinkArgs) == 112 && offsetof(SinkArgs, nmax) == 80 && offsetof(SinkArgs, sleep) == 96,
+              "SinkArgs: kernarg layout the Sinkhorn kernels were tuned at");
+
+// Which Sinkhorn kernel a handle runs, decided once at create (sinkhorn_plan) and handed to every launch.
+//   Slab / SlabScratch: sinkhorn_kernel, row and column slabs in LDS / read from global (cpl, cplT)
+//   Sc / Sc10: sinkhorn_sc_kernel, nmax + 1 <= 448 (rpw 8, 4, 2 or 1 rows per wave) / <= 640 (rpw 3)
+//   Wide: sinkhorn_w_kernel, 640 < nmax + 1 <= 2112
+enum class SinkKind { Slab, SlabScratch, Sc, Sc10, Wide };
+struct SinkPlan {
+  SinkKind kind;
+  int G;    // workgroups per pair
+  int rpw;  // rows per wave of the scaling-form kernels (0: slab kernel)
+  size_t ug_granules, vg_granules;  // exchange buffers of the handle (all max_batch pairs)
+};
+// kind_override: nullptr / "sc" / "slab" (RSPL_SG_SINK); G_override: 0 or the workgroups per pair (RSPL_SG_SINK_G),
+// which applies to Sc, Sc10 and an explicit "slab".  Pure host arithmetic.  False: max_batch exceeds what ncu CUs
+// keep co-resident.
+bool sinkhorn_plan(int nmax, int B, int ncu, const char* kind_override, int G_override, SinkPlan* out);
 
 struct DecodeArgs {
   const float* Z;     // [B][ld*ld]
@@ -151,7 +163,7 @@ hipError_t gemm(const GemmArgs& a, int batch, hipStream_t s);
 // Wt[n][k] = (fp16) W[k][n] for a [K][N] fp32 weight (one-time, at create)
 hipError_t to_half_t(const float* W, int K, int N, _Float16* Wt, hipStream_t s);
 hipError_t to_frag(const _Float16* Wt, int N, int K, _Float16* out, hipStream_t s);
-hipError_t gemm_h(const GemmHArgs& a, int mode, hipStream_t s);
+hipError_t gemm_h(const GemmHArgs& a, hipStream_t s);
 hipError_t gnn_layer(const LayerArgs& a, int B, hipStream_t s);
 // fp32 -> fp16, n elements
 hipError_t to_half(const float* x, _Float16* y, size_t n, hipStream_t s);
@@ -159,21 +171,10 @@ hipError_t prep(const PrepArgs& a, hipStream_t s);
 hipError_t attention(const AttnArgs& a, int B, hipStream_t s);
 hipError_t bins(const BinsArgs& a, int B, hipStream_t s);
 // t0 / t1 (may be null): events stamped with the kernel's own start / end (hipExtLaunchKernelGGL)
-hipError_t sinkhorn(const SinkArgs& a, int B, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// hipErrorInvalidValue if the plan's G does not fit the kernel its kind names (nothing is launched)
+hipError_t sinkhorn(const SinkArgs& a, const SinkPlan& plan, int B, hipStream_t s, hipEvent_t t0 = nullptr,
+                    hipEvent_t t1 = nullptr);
 hipError_t decode(const DecodeArgs& a, int B, hipStream_t s);
-// LDS bytes of one Sinkhorn workgroup (with or without the row / column slabs)
-size_t sinkhorn_lds_bytes(int nmax, int G, bool slabs);
-// rows per wave of the row-block Sinkhorn for G workgroups per pair (0: not supported)
-int sinkhorn_rb_rpw(int nmax, int G);
-// the scaling-form kernel for 448 < nmax + 1 <= 640 (ten 64-column sets per lane) takes this G
-bool sinkhorn_sc10_ok(int nmax, int G);
-// the wide two-hop scaling-form kernel (640 < nmax + 1 <= 2112): its workgroups per pair, the check, and
-// its exchange buffers in granules per pair (hop 1 -> ug, hop 2 -> vg)
-int sinkhorn_wide_groups(int nmax);
-bool sinkhorn_wide_ok(int nmax, int G);
-size_t sinkhorn_wide_hop1_len(int nmax);
-size_t sinkhorn_wide_hop2_len(int nmax);
-constexpr size_t kSinkLdsMax = 150 * 1024;  // slab budget per workgroup (160 KB LDS per CU)
 
 }  // namespace sg
 }  // namespace rspl

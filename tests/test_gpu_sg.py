@@ -317,6 +317,54 @@ def test_sinkhorn_wide_vs_oracle(pkg, weight_blobs, M, N, scale):
         np.testing.assert_allclose(Z, oracle.log_optimal_transport(S, 1.0, it), atol=1e-4, rtol=0)
 
 
+def _plan_scores(nmax):
+    """Seeded N(0, 1) scores, max_keypoints x (max_keypoints - 30)."""
+    return np.random.default_rng(1000 + nmax).normal(size=(nmax, nmax - 30)).astype(np.float32)
+
+
+@pytest.mark.parametrize("nmax,kind", [(447, "sc"), (448, "sc10"), (639, "sc10"), (640, "wide")])
+def test_sinkhorn_plan_boundaries_vs_oracle(pkg, weight_blobs, monkeypatch, nmax, kind):
+    """Handles on either side of the two thresholds of the Sinkhorn plan (nmax + 1 = 448 | 449: seven lane sets
+    exactly full | the ten-set instantiation; 640 | 641: ten sets exactly full | the wide kernel, whose 21 column
+    owners then hold 31 columns each): the kernel the plan names for the device's own CU count, then Z against
+    the oracle's log-domain Sinkhorn (superglue.py:185-205) after 100 iterations and after none (Z = C - norm),
+    at the atol 1e-4 the project uses at score scale 1."""
+    from rspl_slam_amd import api
+    monkeypatch.delenv("RSPL_SG_SINK", raising=False)
+    monkeypatch.delenv("RSPL_SG_SINK_G", raising=False)
+    assert api.sinkhorn_plan(nmax, 1)["kind"] == kind
+    S = _plan_scores(nmax)
+    sg = _sg(pkg, weight_blobs[1], nmax=nmax)
+    for it in (100, 0):
+        ok, Z = sg.debug_sinkhorn(S, 1.0, it)
+        assert ok, sg.error
+        Zr = oracle.log_optimal_transport(S, 1.0, it)
+        print(f"plan boundary nmax={nmax} ({kind}) iters={it}: max |dZ| {np.abs(Z - Zr).max():.3g}")
+        np.testing.assert_allclose(Z, Zr, atol=1e-4, rtol=0)
+    assert sg.status() == (True, 0)
+
+
+def test_sinkhorn_slab_scratch_vs_oracle(pkg, weight_blobs, monkeypatch):
+    """The slab kernel reading its slabs from global memory (sinkhorn_kernel<false>: rows in place, columns from
+    the transposed cplT copy) -- what every handle above 2111 keypoints runs -- at the smallest handle whose slabs
+    exceed the LDS budget: 240 keypoints on two workgroups (2 x 121 x 241 floats), a two-workgroup exchange.
+    Z against the oracle's log-domain Sinkhorn after 100, 1 and 0 iterations at atol 1e-4."""
+    from rspl_slam_amd import api
+    monkeypatch.setenv("RSPL_SG_SINK", "slab")
+    monkeypatch.setenv("RSPL_SG_SINK_G", "2")
+    pl = api.sinkhorn_plan(240, 1)
+    assert (pl["kind"], pl["groups"]) == ("slab_scratch", 2)
+    S = np.random.default_rng(240).normal(size=(240, 230)).astype(np.float32)
+    sg = _sg(pkg, weight_blobs[1], nmax=240)
+    for it in (100, 1, 0):
+        ok, Z = sg.debug_sinkhorn(S, 1.0, it)
+        assert ok, sg.error
+        Zr = oracle.log_optimal_transport(S, 1.0, it)
+        print(f"slab scratch iters={it}: max |dZ| {np.abs(Z - Zr).max():.3g}")
+        np.testing.assert_allclose(Z, Zr, atol=1e-4, rtol=0)
+    assert sg.status() == (True, 0)
+
+
 def _pm(pkg, blob, precision):
     return pkg.PointMatching(pkg.SuperGlueConfig(image_width=752, image_height=480, weights=blob, max_keypoints=400,
                                                  max_batch=1, precision=precision))
