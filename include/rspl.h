@@ -823,6 +823,157 @@ int rspl_track_enqueue(rspl_track* h, int batch, const rspl_track_frame* frames,
 /* Wait for the last enqueue and copy its results out: results[b] receives frame b. */
 int rspl_track_fetch(rspl_track* h, rspl_track_result* results);
 int rspl_track_debug_stage(rspl_track* h, int frame, rspl_track_debug* out);
+/* The DEVICE arrays of keyframe slot `slot` (points [max_keypoints][3], state, track id), for a producer
+ * on the device (rspl_kf_enqueue's d_table_*); sets the slot's keypoint count to n0 as
+ * rspl_track_set_keyframe does.  The producer and rspl_track_enqueue must be stream-ordered.  The
+ * arrays can be read back with rspl_memcpy_d2h. */
+int rspl_track_keyframe_table(rspl_track* h, int slot, int n0, double** d_points, uint8_t** d_state,
+                              int32_t** d_track_id);
+
+/* ------------------------------------------------------------------------ */
+/* Keyframe insertion, device side: what turns a tracked stereo frame into a */
+/* keyframe between SuperGlue and the map, for a batch of independent frames */
+/* as ONE launch behind SuperGlue's stereo pair on the caller's stream:      */
+/*   mutual check            src/point_matching.cc:24-31                     */
+/*   disparity window, u_right, depth   Frame::AddRightFeatures,             */
+/*                           src/frame.cc:157-177 (its return value is       */
+/*                           n_stereo_matches).  The depth is bf / (xl - xr) */
+/*                           with the SIGNED difference: a right keypoint to */
+/*                           the right of its partner passes the |dx| window,*/
+/*                           gets a positive u_right and a negative depth,   */
+/*                           and fails Frame::BackProjectPoint (:313)        */
+/*   new track ids           MapBuilder::InsertKeyframe,                     */
+/*                           src/map_builder.cc:660-665; with init = 1       */
+/*                           MapBuilder::Init's order (:390-403): the        */
+/*                           keypoints with depth > 0 first, then the rest   */
+/*                           (the track ids passed in are ignored)           */
+/*   new map points          Map::InsertKeyframe, src/map.cc:40-55, with     */
+/*                           Camera::BackProjectStereo (src/camera.cc:150-161)*/
+/*   the tracker's keyframe table (rspl_track_keyframe_table), optionally    */
+/* rspl_kf_enqueue never waits for the device; rspl_kf_fetch waits for the   */
+/* one event the enqueue recorded.  One enqueue is in flight per handle.     */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  int max_batch;             /* frames per enqueue */
+  int max_keypoints;         /* keypoints per image */
+  int max_tri_points;        /* map points per rspl_kf_triangulate call (0: none) */
+  int max_tri_observations;  /* observers, and poses, per rspl_kf_triangulate call */
+  int device;
+} rspl_kf_config;
+
+typedef struct {
+  const double* d_features_left;   /* DEVICE SuperPoint records [cap][259] (x, y = rows 1, 2) */
+  const double* d_features_right;
+  const int32_t* d_n_left;         /* DEVICE keypoint counts (clamped to max_keypoints) */
+  const int32_t* d_n_right;
+  const int32_t* d_idx0;           /* DEVICE SuperGlue indices0 [n_left]: left -> right */
+  const int32_t* d_idx1;           /* DEVICE SuperGlue indices1 [n_right]: right -> left */
+  /* host arrays of n entries, copied before the call returns; a keypoint past n has no id and no point */
+  int n;
+  const int32_t* track_id;         /* Frame::GetAllTrackIds, or NULL: all -1 */
+  const int32_t* point_slot;       /* id of the map point the frame holds at the keypoint or -1; NULL: all -1 */
+  const double* points;            /* [n][3] positions of the held points (with point_slot) */
+  const uint8_t* state;            /* [n] RSPL_TRACK_* of the held points (with point_slot) */
+  double fx, fy, cx, cy, bf;
+  double min_x_diff, max_x_diff, max_y_diff;  /* Camera::MinXDiff / MaxXDiff / MaxYDiff */
+  double Twc[16];                  /* Frame::GetPose, row-major 4x4 */
+  int next_track_id;               /* MapBuilder::_track_id */
+  int init;                        /* 1: MapBuilder::Init's id order, no map point without a depth */
+  /* the tracker slot to fill (rspl_track_keyframe_table), all three or none: per keypoint the held
+   * point's position and state or the new point's (RSPL_TRACK_NOT_GOOD for UnTriangulated,
+   * RSPL_TRACK_NO_MAPPOINT where there is none) and the final track id */
+  double* d_table_points;
+  uint8_t* d_table_state;
+  int32_t* d_table_track_id;
+  int table_capacity;              /* entries the three arrays hold (the tracker's max_keypoints) */
+} rspl_kf_frame;
+
+#define RSPL_KF_NEW_NONE 0
+#define RSPL_KF_NEW_GOOD 1            /* a new map point with a stereo position */
+#define RSPL_KF_NEW_UNTRIANGULATED 2  /* a new map point without a position */
+
+typedef struct {
+  int n_keypoints;       /* left keypoints as the device read them */
+  int n_matches;         /* mutual matches */
+  int n_stereo_matches;  /* those inside the disparity window: AddRightFeatures' return value */
+  int n_new_ids, n_new_points, n_new_good;
+  int next_track_id;     /* the next free id */
+  /* per left keypoint, caller arrays of max_keypoints entries (each may be NULL); the first n_keypoints
+   * are written */
+  double* u_right;       /* -1 without a kept match */
+  double* depth;
+  int32_t* track_id;
+  uint8_t* new_point;    /* RSPL_KF_NEW_* */
+  double* new_position;  /* [.][3], zeros unless RSPL_KF_NEW_GOOD */
+} rspl_kf_result;
+
+typedef struct rspl_kf rspl_kf;
+int rspl_kf_create(const rspl_kf_config* cfg, rspl_kf** out);
+void rspl_kf_destroy(rspl_kf* h);
+int rspl_kf_enqueue(rspl_kf* h, int batch, const rspl_kf_frame* frames, void* stream);
+int rspl_kf_fetch(rspl_kf* h, rspl_kf_result* results);
+
+/* Map::TriangulateMappoint (src/map.cc:292-339) for n_points map points in one launch and one
+ * synchronisation: poses Twc [n_poses][16] row-major, camera = fx fy cx cy, and a CSR of observers per
+ * point in ascending frame id -- offsets [n_points + 1], obs_pose (index into Twc, or -1 for an
+ * observer to skip: a frame that is not in the map) and obs_xy [.][2] (the keypoint).  Out: position
+ * [n_points][3] and status [n_points] (RSPL_KF_TRI_*; the reference returns false for both failures).
+ * The rank test is Eigen::ColPivHouseholderQR's with the threshold 1e-5.  h = NULL runs the host
+ * instantiation of the same routine (csrc/kf_triangulate.hpp); the two agree bit for bit.
+ * Deviation: Frame::GetKeypointPosition accepts idx == cols (src/frame.cc:215) and would read out of
+ * bounds; callers pass a keypoint index >= the frame's keypoint count as an observer to skip. */
+#define RSPL_KF_TRI_FEW 0   /* fewer than 2 valid observers */
+#define RSPL_KF_TRI_OK 1
+#define RSPL_KF_TRI_RANK 2  /* rank < 3 */
+int rspl_kf_triangulate(rspl_kf* h, int n_poses, const double* Twc, const double* camera, int n_points,
+                        const int32_t* offsets, const int32_t* obs_pose, const double* obs_xy, double* position,
+                        uint8_t* status);
+
+/* ------------------------------------------------------------------------ */
+/* Keyframe insertion, map side: Map::InsertKeyframe (src/map.cc:24-109) in  */
+/* one call, after MapBuilder::InsertKeyframe's line track ids               */
+/* (src/map_builder.cc:668-673): the keyframe (:26-28), new map points from  */
+/* `tracks` and AddObverser (:40-56), Map::TriangulateMappoint (:292-339)    */
+/* for every UnTriangulated point with more than two observers (:57-59) as   */
+/* one rspl_kf_triangulate batch on `kfh` (NULL: on the host), new map lines */
+/* and observers (:68-92; Frame::TriangulateStereoLine returns false         */
+/* unconditionally, src/frame.cc:443), Map::TriangulateMaplineByMappoints    */
+/* (:341-419, host; cv::fitLine(DIST_L2) restated, parity unpinned) and, when*/
+/* `ba` is given and the map has two keyframes, Map::LocalMapOptimization.   */
+/* The first keyframe (:29) gets what MapBuilder::Init gives it              */
+/* (src/map_builder.cc:390-437): its new points and lines with their         */
+/* observers, no triangulation, no optimisation.                             */
+/* Deviation: the reference silently replaces a map entry whose id exists    */
+/* and orphans its observers; here a new landmark whose id is already in the */
+/* map returns RSPL_E_ARG, before the map changes.                           */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  /* per keypoint [n_keypoints]: the rspl_kf result, unchanged */
+  const int32_t* track_id;
+  const int32_t* point_slot;     /* id of the map point the frame holds or -1 */
+  const uint8_t* new_point;      /* RSPL_KF_NEW_*; the new point's id is the track id */
+  const double* new_position;    /* [.][3] */
+  /* per line [n_lines] (each may be NULL: all -1) */
+  const int32_t* line_track_id;  /* Frame::GetAllLineTrackId; < 0 takes the next id, ascending */
+  const int32_t* line_slot;      /* id of the map line the frame holds or -1 */
+  int* next_line_track_id;       /* MapBuilder::_line_track_id, in and out */
+} rspl_map_tracks;
+
+typedef struct {
+  int n_new_points, n_new_lines;
+  int n_tri_candidates, n_tri_ok, n_tri_rank_failures;
+  int n_lines_triangulated;
+  int optimized;                 /* 1: LocalMapOptimization ran; `optimization` is its report */
+  double bookkeeping_us;         /* host wall time: keyframe, landmarks, observers, line triangulation */
+  double triangulation_us;       /* the point-triangulation batch */
+  rspl_map_report optimization;
+} rspl_map_insert_report;
+
+int rspl_map_insert_keyframe(rspl_map* m, const rspl_map_keyframe* kf, const rspl_map_tracks* tracks, rspl_kf* kfh,
+                             rspl_ba* ba, rspl_map_insert_report* report);
+/* a map line's observers in ascending frame id: the line index and Mapline::GetObverserEndpointStatus */
+int rspl_map_get_mapline_observers(const rspl_map* m, int id, int32_t* frames, int32_t* lines,
+                                   int32_t* endpoint_status, int cap, int* n_observers);
 
 #ifdef __cplusplus
 }

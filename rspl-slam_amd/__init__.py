@@ -11,7 +11,7 @@ from . import capi, weights, synthetic, ba_types, hostgroup, mapping, trajectory
 _API = ("SuperPoint", "SuperPointConfig", "SuperGlue", "SuperGlueConfig", "PointMatching",
         "LocalmapOptimization", "LocalBA", "FrameOptimization", "FrameBA",
         "ShardGroup", "Comm", "comm_unique_id", "broadcast_comm_id", "PnP", "SolvePnPWithCV",
-        "Tracker", "TrackFrame")
+        "Tracker", "TrackFrame", "KeyframeBuilder", "triangulate_points", "stereo_window")
 
 
 def __getattr__(name):

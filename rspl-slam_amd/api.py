@@ -732,10 +732,136 @@ class Tracker:
                     pnp_inlier=a["pnp_inlier"][:n], seed_q=np.array(D.seed_q[:]), seed_p=np.array(D.seed_p[:]),
                     pnp_used=bool(D.pnp_used), edge_inlier=a["edge_inlier"][:n])
 
+    def keyframe_table(self, slot, n0):
+        """The device arrays of keyframe slot ``slot`` (points, state, track id) for a producer on the
+        device (KeyframeBuilder.enqueue's ``table``); sets the slot's keypoint count to ``n0``."""
+        p, s, t = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        capi.check(self._lib.rspl_track_keyframe_table(self._h, slot, n0, C.byref(p), C.byref(s), C.byref(t)),
+                   "rspl_track_keyframe_table")
+        return dict(points=p.value, state=s.value, track_id=t.value, capacity=self.max_keypoints)
+
+    def debug_keyframe_table(self, slot, n0):
+        """Slot ``slot``'s first ``n0`` table entries read back: (points [n0, 3], state, track_id)."""
+        t = self.keyframe_table(slot, n0)
+        pts, st, tid = np.zeros((n0, 3)), np.zeros(n0, np.uint8), np.zeros(n0, np.int32)
+        for a, k in ((pts, "points"), (st, "state"), (tid, "track_id")):
+            if a.nbytes:
+                capi.check(self._lib.rspl_memcpy_d2h(a.ctypes.data, t[k], a.nbytes, None), "rspl_memcpy_d2h")
+        return pts, st, tid
+
     def __del__(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.rspl_track_destroy(self._h)
             self._h = C.c_void_p()
+
+
+from .synthetic import stereo_window  # noqa: E402  (Camera's disparity window from bf and the depth thresholds)
+
+KF_NEW_NONE, KF_NEW_GOOD, KF_NEW_UNTRIANGULATED = 0, 1, 2  # RSPL_KF_NEW_*
+KF_TRI_FEW, KF_TRI_OK, KF_TRI_RANK = 0, 1, 2               # RSPL_KF_TRI_*
+
+
+class KeyframeBuilder:
+    """Owns one rspl_kf handle: SuperGlue's device indices of a stereo pair -> u_right, depth, new track
+    ids, new map points and (optionally) a Tracker slot, for a batch of independent frames in one launch
+    (MapBuilder::InsertKeyframe, Frame::AddRightFeatures, the map-point half of Map::InsertKeyframe); and
+    Map::TriangulateMappoint as one batched call.  ``enqueue`` never waits for the device."""
+
+    def __init__(self, max_batch=1, max_keypoints=1024, max_tri_points=4096, max_tri_observations=65536, device=0):
+        if max_batch <= 0 or max_keypoints <= 0 or max_tri_points < 0 or max_tri_observations < 0:
+            raise ValueError(f"KeyframeBuilder: bad capacities {max_batch}, {max_keypoints}, {max_tri_points}, "
+                             f"{max_tri_observations}")
+        self.max_batch, self.max_keypoints = int(max_batch), int(max_keypoints)
+        self._lib = capi.load()
+        self._h = C.c_void_p()
+        cfg = capi.KfConfig(self.max_batch, self.max_keypoints, int(max_tri_points), int(max_tri_observations), device)
+        capi.check(self._lib.rspl_kf_create(C.byref(cfg), C.byref(self._h)), "rspl_kf_create")
+        self._batch = 0
+
+    def enqueue(self, frames, stream=None):
+        """frames: list of dicts with the device addresses ``d_features_left``, ``d_features_right``,
+        ``d_n_left``, ``d_n_right``, ``d_idx0``, ``d_idx1`` (ints or capi.DeviceBuffer), ``cam`` = (fx, fy, cx,
+        cy, bf), ``Twc`` [4, 4], ``next_track_id``, and optional ``window`` = (min_x_diff, max_x_diff,
+        max_y_diff; default stereo_window(bf)), ``init`` (False), the host arrays ``track_id``, ``point_slot``, ``points``, ``state`` and
+        ``table`` (Tracker.keyframe_table's dict)."""
+        F = (capi.KfFrameDesc * max(len(frames), 1))()
+        keep = []
+        for f, d in zip(F, frames):
+            for k in ("d_features_left", "d_features_right", "d_n_left", "d_n_right", "d_idx0", "d_idx1"):
+                v = d.get(k)
+                setattr(f, k, v.ptr if isinstance(v, capi.DeviceBuffer) else v)
+            n = 0
+            for k, dt in (("track_id", np.int32), ("point_slot", np.int32), ("points", np.float64), ("state", np.uint8)):
+                if d.get(k) is not None:
+                    a = np.ascontiguousarray(d[k], dt)
+                    keep.append(a)
+                    setattr(f, k, a.ctypes.data)
+                    n = max(n, len(a))
+            f.n = n
+            f.fx, f.fy, f.cx, f.cy, f.bf = [float(x) for x in d["cam"]]
+            f.min_x_diff, f.max_x_diff, f.max_y_diff = [float(x) for x in d.get("window") or stereo_window(f.bf)]
+            f.Twc[:] = list(np.asarray(d["Twc"], np.float64).reshape(16))
+            f.next_track_id = int(d.get("next_track_id", 0))
+            f.init = int(bool(d.get("init", False)))
+            t = d.get("table")
+            if t is not None:
+                f.d_table_points, f.d_table_state, f.d_table_track_id = t["points"], t["state"], t["track_id"]
+                f.table_capacity = t["capacity"]
+        capi.check(self._lib.rspl_kf_enqueue(self._h, len(frames), F, _stream_handle(stream)), "rspl_kf_enqueue")
+        self._batch = len(frames)
+
+    def fetch(self):
+        """Wait for the last enqueue.  One dict per frame: the counts n_keypoints, n_matches,
+        n_stereo_matches, n_new_ids, n_new_points, n_new_good, next_track_id and, per left keypoint, u_right,
+        depth, track_id, new_point (KF_NEW_*), new_position [n, 3]."""
+        if self._batch == 0:
+            return []
+        K = self.max_keypoints
+        R = (capi.KfResult * self._batch)()
+        arrs = []
+        for r in R:
+            a = dict(u_right=np.zeros(K), depth=np.zeros(K), track_id=np.zeros(K, np.int32),
+                     new_point=np.zeros(K, np.uint8), new_position=np.zeros((K, 3)))
+            for k, v in a.items():
+                setattr(r, k, v.ctypes.data)
+            arrs.append(a)
+        capi.check(self._lib.rspl_kf_fetch(self._h, R), "rspl_kf_fetch")
+        self._batch = 0
+        out = []
+        for r, a in zip(R, arrs):
+            n = r.n_keypoints
+            d = {k: getattr(r, k) for k in ("n_keypoints", "n_matches", "n_stereo_matches", "n_new_ids",
+                                            "n_new_points", "n_new_good", "next_track_id")}
+            d.update({k: v[:n].copy() for k, v in a.items()})
+            out.append(d)
+        return out
+
+    def triangulate(self, Twc, camera, offsets, obs_pose, obs_xy, host=False):
+        """Map::TriangulateMappoint for len(offsets) - 1 points (a CSR of observers in ascending frame id;
+        obs_pose -1 skips one).  ``host``: the host instantiation of the same routine.  Returns (position
+        [n, 3], status [n] KF_TRI_*)."""
+        return triangulate_points(Twc, camera, offsets, obs_pose, obs_xy, None if host else self)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.rspl_kf_destroy(self._h)
+            self._h = C.c_void_p()
+
+
+def triangulate_points(Twc, camera, offsets, obs_pose, obs_xy, kf: Optional[KeyframeBuilder] = None):
+    """rspl_kf_triangulate; ``kf`` None runs the host instantiation (no device is touched)."""
+    T = np.ascontiguousarray(Twc, np.float64).reshape(-1, 16)
+    cam = np.ascontiguousarray(camera, np.float64)[:4].copy()
+    off = np.ascontiguousarray(offsets, np.int32)
+    op = np.ascontiguousarray(obs_pose, np.int32)
+    xy = np.ascontiguousarray(obs_xy, np.float64).reshape(-1, 2)
+    n = len(off) - 1
+    pos, st = np.zeros((max(n, 0), 3)), np.zeros(max(n, 0), np.uint8)
+    lib = capi.load()
+    capi.check(lib.rspl_kf_triangulate(kf._h if kf is not None else None, len(T), T.ctypes.data, cam.ctypes.data, n,
+                                       off.ctypes.data, op.ctypes.data, xy.ctypes.data, pos.ctypes.data,
+                                       st.ctypes.data), "rspl_kf_triangulate")
+    return pos, st
 
 
 def _stream_handle(stream):

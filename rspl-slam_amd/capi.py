@@ -48,7 +48,9 @@ EXPORTS = [
     "rspl_lines_stereo", "rspl_lines_stereo_device", "rspl_lines_status", "rspl_lines_detect",
     "rspl_lines_debug_canny",
     "rspl_track_create", "rspl_track_destroy", "rspl_track_set_keyframe", "rspl_track_enqueue", "rspl_track_fetch",
-    "rspl_track_debug_stage",
+    "rspl_track_debug_stage", "rspl_track_keyframe_table",
+    "rspl_kf_create", "rspl_kf_destroy", "rspl_kf_enqueue", "rspl_kf_fetch", "rspl_kf_triangulate",
+    "rspl_map_insert_keyframe", "rspl_map_get_mapline_observers",
 ]
 
 
@@ -125,6 +127,29 @@ class TrackDebug(C.Structure):
                 ("pnp_n_inliers", C.c_int), ("pnp_hypotheses", C.c_int), ("pnp_inlier", C.c_void_p),
                 ("seed_q", C.c_double * 4), ("seed_p", C.c_double * 3), ("pnp_used", C.c_int),
                 ("edge_inlier", C.c_void_p)]
+
+
+class KfConfig(C.Structure):
+    _fields_ = [("max_batch", C.c_int), ("max_keypoints", C.c_int), ("max_tri_points", C.c_int),
+                ("max_tri_observations", C.c_int), ("device", C.c_int)]
+
+
+class KfFrameDesc(C.Structure):
+    _fields_ = [("d_features_left", C.c_void_p), ("d_features_right", C.c_void_p), ("d_n_left", C.c_void_p),
+                ("d_n_right", C.c_void_p), ("d_idx0", C.c_void_p), ("d_idx1", C.c_void_p), ("n", C.c_int),
+                ("track_id", C.c_void_p), ("point_slot", C.c_void_p), ("points", C.c_void_p), ("state", C.c_void_p),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("bf", C.c_double),
+                ("min_x_diff", C.c_double), ("max_x_diff", C.c_double), ("max_y_diff", C.c_double),
+                ("Twc", C.c_double * 16), ("next_track_id", C.c_int), ("init", C.c_int),
+                ("d_table_points", C.c_void_p), ("d_table_state", C.c_void_p), ("d_table_track_id", C.c_void_p),
+                ("table_capacity", C.c_int)]
+
+
+class KfResult(C.Structure):
+    _fields_ = [("n_keypoints", C.c_int), ("n_matches", C.c_int), ("n_stereo_matches", C.c_int),
+                ("n_new_ids", C.c_int), ("n_new_points", C.c_int), ("n_new_good", C.c_int),
+                ("next_track_id", C.c_int), ("u_right", C.c_void_p), ("depth", C.c_void_p), ("track_id", C.c_void_p),
+                ("new_point", C.c_void_p), ("new_position", C.c_void_p)]
 
 
 class RsplError(RuntimeError):
@@ -241,6 +266,14 @@ def load(path: pathlib.Path = LIB_PATH):
         lib.rspl_track_enqueue.argtypes = [vp, ip, vp, vp]
         lib.rspl_track_fetch.argtypes = [vp, vp]
         lib.rspl_track_debug_stage.argtypes = [vp, ip, C.POINTER(TrackDebug)]
+    if hasattr(lib, "rspl_kf_create"):
+        lib.rspl_track_keyframe_table.argtypes = [vp, ip, ip, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        lib.rspl_kf_create.argtypes = [C.POINTER(KfConfig), C.POINTER(vp)]
+        lib.rspl_kf_destroy.argtypes = [vp]
+        lib.rspl_kf_destroy.restype = None
+        lib.rspl_kf_enqueue.argtypes = [vp, ip, vp, vp]
+        lib.rspl_kf_fetch.argtypes = [vp, vp]
+        lib.rspl_kf_triangulate.argtypes = [vp, ip, vp, vp, ip, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -283,8 +283,7 @@ __global__ __launch_bounds__(1024) void stereo_filter_kernel(StereoArgs a) {
       if (t >= 0 && t < nr) {
         const double* l = a.pts + (size_t)q * a.stride + a.xoff;
         const double* r = a.pts + a.pt_batch + (size_t)t * a.stride + a.xoff;
-        const double dx = fabs(l[0] - r[0]), dy = fabs(l[1] - r[1]);
-        keep = dx > a.min_x && dx < a.max_x && dy <= a.max_y;
+        keep = in_disparity_window(l[0], l[1], r[0], r[1], a.min_x, a.max_x, a.max_y);
       }
     }
     const unsigned long long bal = __ballot(keep);

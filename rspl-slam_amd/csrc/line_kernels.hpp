@@ -47,6 +47,13 @@ struct MatchArgs {
   const int* status;     // AssignArgs::status of the sets (nullable): an overflowed set matches nothing
 };
 
+// the disparity window of Frame::AddRightFeatures (frame.cc:161-164): strict in x, inclusive in y
+__host__ __device__ __forceinline__ bool in_disparity_window(double xl, double yl, double xr, double yr, double min_x,
+                                                             double max_x, double max_y) {
+  const double dx = fabs(xl - xr), dy = fabs(yl - yr);
+  return dx > min_x && dx < max_x && dy <= max_y;
+}
+
 // Frame::AddRightFeatures' stereo filter (frame.cc:157-167) on the device: the SuperGlue match
 // index of each left keypoint (idx[q] = right keypoint or -1) -> (q, t) pairs inside the disparity
 // window, compacted in any order (MatchLines only counts them) into matches, count into *n_out.

@@ -937,8 +937,321 @@ struct rspl_map {
 };
 
 // ---------------------------------------------------------------------------------------------
+// Map::InsertKeyframe's landmark half (map.cc:31-102): line fit and line triangulation on the host
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct P3f {
+  float x, y, z;
+};
+
+// cv::fitLine(points, DIST_L2) for 3-D points, restated from the published algorithm (OpenCV is not a
+// dependency, so the parity of this function is unpinned): raw moments and the mean in float, the central
+// second moments, the matrix whose smallest eigenvector is the principal axis of the scatter, and that
+// eigenvector by a cyclic Jacobi (8 sweeps over (0,1), (0,2), (1,2), rational rotations: + - * / sqrt
+// only, all in float).  line = direction (unit) | mean.
+void fit_line_l2(const std::vector<P3f>& pts, float* line) {
+#pragma clang fp contract(off)
+  float x0 = 0, y0 = 0, z0 = 0, x2 = 0, y2 = 0, z2 = 0, xy = 0, yz = 0, xz = 0;
+  for (const P3f& p : pts) {
+    x2 += p.x * p.x; y2 += p.y * p.y; z2 += p.z * p.z;
+    xy += p.x * p.y; yz += p.y * p.z; xz += p.x * p.z;
+    x0 += p.x; y0 += p.y; z0 += p.z;
+  }
+  const float w0 = (float)pts.size();
+  x2 /= w0; y2 /= w0; z2 /= w0; xy /= w0; yz /= w0; xz /= w0; x0 /= w0; y0 /= w0; z0 /= w0;
+  const float dx2 = x2 - x0 * x0, dy2 = y2 - y0 * y0, dz2 = z2 - z0 * z0;
+  const float dxy = xy - x0 * y0, dxz = xz - x0 * z0, dyz = yz - y0 * z0;
+  float a[3][3] = {{dz2 + dy2, -dxy, -dxz}, {-dxy, dx2 + dz2, -dyz}, {-dxz, -dyz, dy2 + dx2}};
+  float v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  static const int PQ[3][3] = {{0, 1, 2}, {0, 2, 1}, {1, 2, 0}};  // p, q and the third index
+  for (int sweep = 0; sweep < 8; sweep++) {
+    for (int k = 0; k < 3; k++) {
+      const int p = PQ[k][0], q = PQ[k][1], r = PQ[k][2];
+      const float apq = a[p][q];
+      if (apq == 0.0f) continue;
+      const float theta = (a[q][q] - a[p][p]) / (2.0f * apq);
+      const float t = (theta >= 0.0f ? 1.0f : -1.0f) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0f));
+      const float c = 1.0f / std::sqrt(t * t + 1.0f), s = t * c;
+      a[p][p] = a[p][p] - t * apq;
+      a[q][q] = a[q][q] + t * apq;
+      a[p][q] = a[q][p] = 0.0f;
+      const float arp = a[r][p], arq = a[r][q];
+      a[r][p] = a[p][r] = c * arp - s * arq;
+      a[r][q] = a[q][r] = s * arp + c * arq;
+      for (int i = 0; i < 3; i++) {
+        const float vip = v[i][p], viq = v[i][q];
+        v[i][p] = c * vip - s * viq;
+        v[i][q] = s * vip + c * viq;
+      }
+    }
+  }
+  const float e0 = a[0][0], e1 = a[1][1], e2 = a[2][2];
+  const int i = e0 < e1 ? (e0 < e2 ? 0 : 2) : (e1 < e2 ? 1 : 2);
+  const float n = (float)std::sqrt((double)v[0][i] * v[0][i] + (double)v[1][i] * v[1][i] + (double)v[2][i] * v[2][i]);
+  line[0] = v[0][i] / n; line[1] = v[1][i] / n; line[2] = v[2][i] / n;
+  line[3] = x0; line[4] = y0; line[5] = z0;
+}
+
+// CVPointLineDistance3D (line_processor.cc:52-75), float
+float point_line_distance(const P3f& p, const float* line) {
+#pragma clang fp contract(off)
+  const float x = p.x - line[3], y = p.y - line[4], z = p.z - line[5];
+  const float c0 = line[1] * z - line[2] * y, c1 = line[2] * x - line[0] * z, c2 = line[0] * y - line[1] * x;
+  return std::sqrt(c0 * c0 + c1 * c1 + c2 * c2);
+}
+
+// g2o::Line3D::fromCartesian (point | direction) -> (w, d)
+void line_from_cartesian(const double* c, double* L) {
+#pragma clang fp contract(off)
+  const double n = std::sqrt(c[3] * c[3] + c[4] * c[4] + c[5] * c[5]);
+  const double d[3] = {c[3] / n, c[4] / n, c[5] / n};
+  const double dp = d[0] * c[0] + d[1] * c[1] + d[2] * c[2];
+  const double p[3] = {c[0] - d[0] * dp, c[1] - d[1] * dp, c[2] - d[2] * dp};
+  const double q[3] = {p[0] + d[0], p[1] + d[1], p[2] + d[2]};
+  L[0] = p[1] * q[2] - p[2] * q[1];
+  L[1] = p[2] * q[0] - p[0] * q[2];
+  L[2] = p[0] * q[1] - p[1] * q[0];
+  L[3] = d[0]; L[4] = d[1]; L[5] = d[2];
+}
+
+// Map::TriangulateMaplineByMappoints (map.cc:341-419)
+bool triangulate_mapline(rspl_map& M, MLine& l) {
+  if (l.type == kGood) return true;
+  if (l.obs.size() < 2) return false;
+  std::vector<P3f> pts;
+  for (auto& kv : l.obs) {
+    MFrame* f = M.frame(kv.first);
+    if (!f) continue;
+    if (kv.second < 0 || kv.second >= (int)f->pol.size()) continue;  // GetPointsOnLine: an empty map
+    for (auto& pd : f->pol[kv.second]) {
+      if (pd.first < 0 || pd.first >= (int)f->mpt.size()) continue;
+      const MPoint* q = M.point(f->mpt[pd.first]);
+      if (!q || q->type != kGood) continue;
+      pts.push_back({(float)q->p[0], (float)q->p[1], (float)q->p[2]});  // cv::Point3f
+    }
+  }
+  if (pts.size() < 2) return false;
+  float line[6];
+  for (int round = 0; round < 4; round++) {
+    fit_line_l2(pts, line);
+    const size_t before = pts.size();
+    size_t inl = 0;
+    for (size_t j = 0; j < before; j++)
+      if ((double)point_line_distance(pts[j], line) < 0.2) pts[inl++] = pts[j];
+    pts.resize(inl);
+    if (inl == before || inl < 3) break;
+  }
+  if (pts.size() < 2) return false;
+  const double cart[6] = {line[3], line[4], line[5], line[0], line[1], line[2]};
+  line_from_cartesian(cart, l.L);
+  l.type = kGood;  // SetLine3D
+  int md = 0;
+  float max_v = std::fabs(line[0]);
+  for (int i = 1; i < 3; i++)
+    if (std::fabs(line[i]) > max_v) {
+      md = i;
+      max_v = std::fabs(line[i]);
+    }
+  // the extreme points along the dominant axis (the reference sorts; on equal coordinates the first wins here)
+  auto co = [&](const P3f& p) { return md == 0 ? p.x : (md == 1 ? p.y : p.z); };
+  size_t lo = 0, hi = 0;
+  for (size_t j = 1; j < pts.size(); j++) {
+    if (co(pts[j]) < co(pts[lo])) lo = j;
+    if (co(pts[j]) > co(pts[hi])) hi = j;
+  }
+  const double ep[6] = {pts[lo].x, pts[lo].y, pts[lo].z, pts[hi].x, pts[hi].y, pts[hi].z};
+  memcpy(l.ep, ep, sizeof(ep));
+  l.ep_valid = true;   // SetEndpoints(endpoints, false)
+  l.to_update = false; // SetEndpointsUpdateStatus(false)
+  for (auto& kv : l.obs)
+    if (M.frame(kv.first)) l.incl[kv.first] = 1;
+  return true;
+}
+
+double us_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
+extern "C" int rspl_map_insert_keyframe(rspl_map* m, const rspl_map_keyframe* k, const rspl_map_tracks* tr,
+                                        rspl_kf* kfh, rspl_ba* ba, rspl_map_insert_report* rep) {
+  RSPL_CHECK_ARG(m && k && tr, "rspl_map_insert_keyframe: NULL argument");
+  RSPL_CHECK_ARG(k->n_keypoints >= 0 && k->n_lines >= 0, "rspl_map_insert_keyframe: negative counts");
+  const int n = k->n_keypoints, nl = k->n_lines, fid = k->frame_id;
+  RSPL_CHECK_ARG(n == 0 || (tr->track_id && tr->point_slot && tr->new_point && tr->new_position),
+                 "rspl_map_insert_keyframe: NULL per-keypoint array");
+  const auto t0 = std::chrono::steady_clock::now();
+  // everything that can be refused is checked before the map changes
+  RSPL_CHECK_ARG(!m->kf.count(fid), "rspl_map_insert_keyframe: frame %d exists", fid);
+  {
+    std::set<int> fresh;
+    for (int i = 0; i < n; i++) {
+      if (tr->point_slot[i] >= 0) {
+        RSPL_CHECK_ARG(m->point(tr->point_slot[i]), "keypoint %d holds map point %d, which is not in the map", i,
+                       tr->point_slot[i]);
+      } else if (tr->new_point[i]) {
+        const int id = tr->track_id[i];
+        RSPL_CHECK_ARG(tr->new_point[i] <= 2 && id >= 0, "keypoint %d: new_point %d with track id %d", i,
+                       tr->new_point[i], id);
+        RSPL_CHECK_ARG(!m->mp.count(id) && fresh.insert(id).second, "new map point %d is already in the map", id);
+      }
+    }
+  }
+  std::vector<int> line_id(nl, -1);
+  {
+    int next = tr->next_line_track_id ? *tr->next_line_track_id : 0;
+    std::set<int> fresh;
+    for (int i = 0; i < nl; i++) {
+      int id = tr->line_track_id ? tr->line_track_id[i] : -1;
+      if (id < 0) {  // map_builder.cc:668-673
+        RSPL_CHECK_ARG(tr->next_line_track_id, "line %d needs a track id and next_line_track_id is NULL", i);
+        id = next++;
+      }
+      line_id[i] = id;
+      const int slot = tr->line_slot ? tr->line_slot[i] : -1;
+      if (slot >= 0) {
+        RSPL_CHECK_ARG(m->line(slot), "line %d holds map line %d, which is not in the map", i, slot);
+      } else {
+        RSPL_CHECK_ARG(!m->ml.count(id) && fresh.insert(id).second, "new map line %d is already in the map", id);
+      }
+    }
+  }
+  int rc = rspl_map_add_keyframe(m, k);  // map.cc:26-28
+  if (rc) return rc;
+  MFrame& f = *m->frame(fid);
+  const bool first = m->kf.size() < 2;  // :29 -- the first keyframe's landmarks are MapBuilder::Init's (below)
+  rspl_map_insert_report R{};
+
+  // map points (:40-60): a new one per keypoint that holds none, the observer, the candidates
+  std::vector<MPoint*> cand;
+  for (int i = 0; i < n; i++) {
+    MPoint* q = nullptr;
+    if (tr->point_slot[i] >= 0) {
+      q = m->point(tr->point_slot[i]);
+    } else if (tr->new_point[i]) {
+      MPoint np;
+      np.id = tr->track_id[i];
+      if (tr->new_point[i] == 1) {  // SetPosition
+        for (int c = 0; c < 3; c++) np.p[c] = tr->new_position[3 * (size_t)i + c];
+        np.type = kGood;
+      }
+      q = &m->mp.emplace(np.id, np).first->second;
+      m->mp_ix.put(np.id, q);
+      R.n_new_points++;
+    } else {
+      continue;
+    }
+    f.mpt[i] = q->id;
+    q->obs[fid] = i;
+    if (!first && q->type == kUnTriangulated && q->observers() > 2) cand.push_back(q);
+  }
+  R.bookkeeping_us = us_since(t0);
+
+  // Map::TriangulateMappoint for every candidate, one batch: a candidate reads its own observers and the
+  // keyframe poses only, so the batch equals the reference's one-by-one calls inside the loop above
+  const auto t1 = std::chrono::steady_clock::now();
+  R.n_tri_candidates = (int)cand.size();
+  if (!cand.empty()) {
+    std::map<int, int> pose_ix;
+    std::vector<double> poses, xy, pos(3 * cand.size());
+    std::vector<int32_t> off(1, 0), op;
+    std::vector<uint8_t> st(cand.size());
+    for (MPoint* q : cand) {
+      for (auto& kv : q->obs) {  // ascending frame id
+        const MFrame* of = m->frame(kv.first);
+        int px = -1;
+        double kp[3] = {0, 0, 0};
+        // (an index >= the frame's keypoint count is an invalid observer: see kf_triangulate.hpp)
+        if (of && kv.second >= 0 && of->keypoint(kv.second, kp)) {
+          auto it = pose_ix.find(kv.first);
+          if (it == pose_ix.end()) {
+            it = pose_ix.emplace(kv.first, (int)pose_ix.size()).first;
+            poses.insert(poses.end(), of->Twc, of->Twc + 16);
+          }
+          px = it->second;
+        }
+        op.push_back(px);
+        xy.push_back(kp[0]);
+        xy.push_back(kp[1]);
+      }
+      off.push_back((int32_t)op.size());
+    }
+    rc = rspl_kf_triangulate(kfh, (int)pose_ix.size(), poses.data(), m->cam, (int)cand.size(), off.data(), op.data(),
+                             xy.data(), pos.data(), st.data());
+    if (rc) return rc;
+    for (size_t c = 0; c < cand.size(); c++) {
+      if (st[c] == 1) {  // SetPosition: UnTriangulated -> Good
+        for (int j = 0; j < 3; j++) cand[c]->p[j] = pos[3 * c + j];
+        cand[c]->type = kGood;
+        R.n_tri_ok++;
+      } else if (st[c] == 2) {
+        R.n_tri_rank_failures++;
+      }
+    }
+  }
+  R.triangulation_us = us_since(t1);
+
+  // map lines (:68-102).  Frame::TriangulateStereoLine returns false unconditionally (frame.cc:443), so a
+  // new line never gets endpoints from stereo.
+  const auto t2 = std::chrono::steady_clock::now();
+  for (int i = 0; i < nl; i++) {
+    MLine* l = nullptr;
+    const int slot = tr->line_slot ? tr->line_slot[i] : -1;
+    if (slot >= 0) {
+      l = m->line(slot);
+    } else {
+      MLine nw;
+      nw.id = line_id[i];
+      l = &m->ml.emplace(nw.id, nw).first->second;
+      m->ml_ix.put(nw.id, l);
+      R.n_new_lines++;
+    }
+    f.mpl[i] = l->id;
+    l->obs[fid] = i;
+    if (l->incl.find(fid) == l->incl.end() || l->incl[fid] < 0) l->incl[fid] = 0;
+    if (!first && l->type == kUnTriangulated && l->observers() >= 2) R.n_lines_triangulated += triangulate_mapline(*m, *l);
+  }
+  if (tr->next_line_track_id) {
+    int next = *tr->next_line_track_id;
+    for (int i = 0; i < nl; i++)
+      if (!tr->line_track_id || tr->line_track_id[i] < 0) next++;
+    *tr->next_line_track_id = next;
+  }
+  R.bookkeeping_us += us_since(t2);
+  if (ba && !first) {  // :105-107
+    rc = m->local_map_optimization(fid, ba, &R.optimization);
+    R.optimized = rc == RSPL_OK;
+  }
+  if (rep) *rep = R;
+  return rc;
+}
+
+extern "C" int rspl_map_get_mapline_observers(const rspl_map* m, int id, int32_t* frames, int32_t* lines,
+                                              int32_t* endpoint_status, int cap, int* n_observers) {
+  RSPL_CHECK_ARG(m, "rspl_map_get_mapline_observers: NULL map");
+  auto it = m->ml.find(id);
+  RSPL_CHECK_ARG(it != m->ml.end(), "rspl_map_get_mapline_observers: unknown map line %d", id);
+  const MLine& l = it->second;
+  if (n_observers) *n_observers = (int)l.obs.size();
+  int i = 0;
+  for (auto& kv : l.obs) {
+    if (i >= cap) break;
+    if (frames) frames[i] = kv.first;
+    if (lines) lines[i] = kv.second;
+    if (endpoint_status) {  // Mapline::GetObverserEndpointStatus
+      auto s = l.incl.find(kv.first);
+      endpoint_status[i] = s == l.incl.end() ? -1 : s->second;
+    }
+    i++;
+  }
+  return RSPL_OK;
+}
+
 extern "C" int rspl_map_create(const rspl_map_config* cfg, rspl_map** out) {
   RSPL_CHECK_ARG(cfg && out && cfg->camera, "rspl_map_create: NULL argument");
   auto* m = new rspl_map();

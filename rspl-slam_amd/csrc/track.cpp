@@ -243,6 +243,22 @@ extern "C" int rspl_track_set_keyframe(rspl_track* h, int slot, int n0, const do
   return RSPL_OK;
 }
 
+extern "C" int rspl_track_keyframe_table(rspl_track* h, int slot, int n0, double** d_points, uint8_t** d_state,
+                                         int32_t** d_track_id) {
+  RSPL_CHECK_ARG(h && d_points && d_state && d_track_id, "rspl_track_keyframe_table: NULL argument");
+  RSPL_CHECK_ARG(slot >= 0 && slot < h->cfg.max_batch, "slot %d outside [0, %d)", slot, h->cfg.max_batch);
+  RSPL_CHECK_ARG(n0 >= 0 && n0 <= h->cfg.max_keypoints, "n0 %d exceeds max_keypoints %d", n0, h->cfg.max_keypoints);
+  RSPL_CHECK_ARG(!h->pending, "rspl_track_keyframe_table: an enqueue is in flight, fetch it first");
+  // an earlier host upload into this slot has to land before a device producer overwrites it
+  RSPL_HIP(hipEventSynchronize(h->kf_ev[slot]));
+  const size_t K = h->cfg.max_keypoints;
+  *d_points = h->kf_points + 3 * K * slot;
+  *d_state = h->kf_state + K * slot;
+  *d_track_id = h->kf_tid + K * slot;
+  h->n0[slot] = n0;
+  return RSPL_OK;
+}
+
 extern "C" int rspl_track_enqueue(rspl_track* h, int batch, const rspl_track_frame* frames, void* stream) {
   RSPL_CHECK_ARG(h && (batch == 0 || frames), "rspl_track_enqueue: NULL argument");
   RSPL_CHECK_ARG(batch >= 0 && batch <= h->cfg.max_batch, "batch %d exceeds max_batch %d", batch, h->cfg.max_batch);

@@ -18,10 +18,7 @@ namespace {
 
 constexpr int T = 256, NW = 4;
 
-// lanes below this one whose bit is set in a wave64 ballot
-__device__ __forceinline__ int lanes_below(unsigned long long m) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
+using wave::lanes_below;
 
 // RANSACPointSetRegistrator::getSubset started at draw k of the (already reduced % count) stream dv[0, nd):
 // 5 distinct values, a duplicate draws again.  Returns the draws consumed, 0 when the table ends first.
@@ -88,8 +85,8 @@ __global__ __launch_bounds__(T) void track_gather_kernel(Args a) {
     int j = -1, t = -1;
     bool keep = false, st = false;
     if (i < n1) {
-      const int jj = P.idx1[i];
-      if (jj >= 0 && jj < P.n0 && P.idx0[jj] == i) {
+      const int jj = mutual_partner(P.idx1, P.idx0, i, P.n0);
+      if (jj >= 0) {
         j = jj;
         t = P.kf_tid[jj];
         keep = P.kf_state[jj] == 1;

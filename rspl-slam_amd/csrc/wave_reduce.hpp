@@ -10,6 +10,12 @@ namespace wave {
 
 constexpr int kNV = 28;  // 21 upper-triangular H entries, 6 b entries, chi2
 
+// lanes below this one whose bit is set in a wave64 ballot (the ordered compactions of track_kernels.hip
+// and kf_kernels.hip)
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
 template <int CTRL>
 __device__ __forceinline__ double dppd(double v) {
   const long long b = __double_as_longlong(v);

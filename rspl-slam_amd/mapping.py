@@ -46,10 +46,30 @@ class MapReport(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class MapTracks(C.Structure):
+    _fields_ = [("track_id", _i32p), ("point_slot", _i32p), ("new_point", _u8p), ("new_position", _dp),
+                ("line_track_id", _i32p), ("line_slot", _i32p), ("next_line_track_id", C.POINTER(C.c_int))]
+
+
+class MapInsertReport(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_new_points", "n_new_lines", "n_tri_candidates", "n_tri_ok",
+                                       "n_tri_rank_failures", "n_lines_triangulated", "optimized")] + \
+               [("bookkeeping_us", C.c_double), ("triangulation_us", C.c_double), ("optimization", MapReport)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f != "optimization"}
+        d["optimization"] = self.optimization.as_dict() if self.optimized else None
+        return d
+
+
 def _declare(lib):
     if getattr(lib, "_rspl_map_declared", False):
         return lib
     vp, ip = C.c_void_p, C.c_int
+    if hasattr(lib, "rspl_map_insert_keyframe"):  # (absent from older builds used as A/B baselines)
+        lib.rspl_map_insert_keyframe.argtypes = [vp, C.POINTER(MapKeyframe), C.POINTER(MapTracks), vp, vp,
+                                                 C.POINTER(MapInsertReport)]
+        lib.rspl_map_get_mapline_observers.argtypes = [vp, ip, _i32p, _i32p, _i32p, ip, C.POINTER(ip)]
     lib.rspl_map_create.argtypes = [C.POINTER(MapConfig), C.POINTER(vp)]
     lib.rspl_map_destroy.argtypes = [vp]
     lib.rspl_map_destroy.restype = None
@@ -108,6 +128,16 @@ class Map:
                        lines_left: Optional[np.ndarray] = None, lines_right: Optional[np.ndarray] = None,
                        lines_right_valid: Optional[np.ndarray] = None,
                        points_on_lines: Optional[List[Dict[int, float]]] = None, parent_id: int = -1):
+        k, _keep = self._keyframe(frame_id, timestamp, Twc, keypoints, lines_left, lines_right, lines_right_valid,
+                                  points_on_lines, parent_id)
+        capi.check(self._lib.rspl_map_add_keyframe(self._h, C.byref(k)), "rspl_map_add_keyframe")
+        self._nkp[frame_id] = k.n_keypoints
+        self._nl[frame_id] = k.n_lines
+
+    @staticmethod
+    def _keyframe(frame_id, timestamp, Twc, keypoints, lines_left, lines_right, lines_right_valid, points_on_lines,
+                  parent_id):
+        """The rspl_map_keyframe record and the arrays it points into."""
         T = np.ascontiguousarray(Twc, np.float64).reshape(16)
         kp = np.ascontiguousarray(keypoints, np.float64).reshape(-1, 3)
         nl = 0 if lines_left is None else len(lines_left)
@@ -124,9 +154,57 @@ class Map:
         k = MapKeyframe(frame_id, timestamp, _p(T, C.c_double), len(kp), _p(kp, C.c_double), nl,
                         _p(ll, C.c_double), _p(lr, C.c_double), _p(lv, C.c_uint8), _p(off, C.c_int32),
                         _p(pts, C.c_int32), _p(dist, C.c_double), parent_id)
-        capi.check(self._lib.rspl_map_add_keyframe(self._h, C.byref(k)), "rspl_map_add_keyframe")
-        self._nkp[frame_id] = len(kp)
+        return k, (T, kp, ll, lr, lv, off, pts, dist)
+
+    def InsertKeyframeFull(self, frame_id: int, timestamp: float, Twc, keypoints, tracks: dict, lines_left=None,
+                           lines_right=None, lines_right_valid=None, points_on_lines=None, parent_id: int = -1,
+                           kf=None, ba=None) -> dict:
+        """Map::InsertKeyframe (map.cc:24-109) in one call (rspl_map_insert_keyframe).  ``tracks``: per
+        keypoint ``track_id``, ``point_slot``, ``new_point``, ``new_position`` (a KeyframeBuilder result,
+        unchanged), per line the optional ``line_track_id`` and ``line_slot``, and ``next_line_track_id``.
+        ``kf``: the KeyframeBuilder whose device triangulates (None: the host instantiation); ``ba``: the
+        LocalBA for LocalMapOptimization (None: stop before it).  Returns the report, with
+        ``next_line_track_id`` and, per line, ``line_ids``."""
+        k, _keep = self._keyframe(frame_id, timestamp, Twc, keypoints, lines_left, lines_right, lines_right_valid,
+                                  points_on_lines, parent_id)
+        n, nl = k.n_keypoints, k.n_lines
+        tid = np.ascontiguousarray(tracks["track_id"], np.int32)
+        slot = np.ascontiguousarray(tracks["point_slot"], np.int32)
+        newp = np.ascontiguousarray(tracks["new_point"], np.uint8)
+        pos = np.ascontiguousarray(tracks["new_position"], np.float64).reshape(-1, 3)
+        if not (len(tid) == len(slot) == len(newp) == len(pos) == n):
+            raise ValueError("InsertKeyframeFull: the per-keypoint arrays do not have one entry per keypoint")
+        ltid = lslot = None
+        if nl and tracks.get("line_track_id") is not None:
+            ltid = np.ascontiguousarray(tracks["line_track_id"], np.int32)
+        if nl and tracks.get("line_slot") is not None:
+            lslot = np.ascontiguousarray(tracks["line_slot"], np.int32)
+        if any(a is not None and len(a) != nl for a in (ltid, lslot)):
+            raise ValueError("InsertKeyframeFull: the per-line arrays do not have one entry per line")
+        nxt = C.c_int(int(tracks.get("next_line_track_id", 0)))
+        t = MapTracks(_p(tid, C.c_int32), _p(slot, C.c_int32), _p(newp, C.c_uint8), _p(pos, C.c_double),
+                      _p(ltid, C.c_int32), _p(lslot, C.c_int32), C.pointer(nxt))
+        r = MapInsertReport()
+        capi.check(self._lib.rspl_map_insert_keyframe(self._h, C.byref(k), C.byref(t), kf._h if kf is not None else None,
+                                                      ba._h if ba is not None else None, C.byref(r)),
+                   "rspl_map_insert_keyframe")
+        self._nkp[frame_id] = n
         self._nl[frame_id] = nl
+        d = r.as_dict()
+        d["next_line_track_id"] = nxt.value
+        d["line_ids"] = self.FrameSlots(frame_id)[1]
+        return d
+
+    def GetMaplineObservers(self, line_id: int):
+        """[(frame id, line index, Mapline::GetObverserEndpointStatus)] in ascending frame id."""
+        n = C.c_int()
+        capi.check(self._lib.rspl_map_get_mapline_observers(self._h, line_id, None, None, None, 0, C.byref(n)),
+                   "rspl_map_get_mapline_observers")
+        fr, li, st = (np.zeros(n.value, np.int32) for _ in range(3))
+        capi.check(self._lib.rspl_map_get_mapline_observers(self._h, line_id, _p(fr, C.c_int32), _p(li, C.c_int32),
+                                                            _p(st, C.c_int32), n.value, C.byref(n)),
+                   "rspl_map_get_mapline_observers")
+        return [(int(a), int(b), int(c)) for a, b, c in zip(fr, li, st)]
 
     def InsertMappoint(self, point_id: int, p, type_: int = GOOD):
         a = np.ascontiguousarray(p, np.float64)

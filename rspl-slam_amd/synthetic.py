@@ -462,6 +462,144 @@ def map_sequence(n_keyframes: int = 30, n_points: int = 6000, n_lines: int = 80,
     return dict(camera=np.array(cam, np.float64), gt_Twc=np.array(gt), timestamps=np.array(ts), keyframes=kfs)
 
 
+def stereo_window(bf, depth_lower_thr=0.1, depth_upper_thr=10.0, max_y_diff=2.0):
+    """(min_x_diff, max_x_diff, max_y_diff) as Camera derives them (camera.cc:21-23, configs/euroc.yaml:9-11)."""
+    return bf / depth_upper_thr, bf / depth_lower_thr, max_y_diff
+
+
+def keyframe_problem(n_left: int = 400, n_right: int = 380, n_common: int = 300, seed: int = 0, need_id: str = "third",
+                     frac_held: float = 0.5, n_non_mutual: int = 8, next_track_id: int = 1000, width: int = 752,
+                     height: int = 480, cam=(EUROC_FX, EUROC_FY, EUROC_CX, EUROC_CY, EUROC_BF)):
+    """Seeded input of the keyframe builder's stereo stage (Frame::AddRightFeatures + the id / map-point half of
+    keyframe insertion): the SuperPoint records of a stereo pair and SuperGlue's two index arrays.
+
+    ``n_common`` mutual pairs in a random permutation; by turns a pair lies inside the disparity window
+    (most), below ``min_x_diff``, above ``max_x_diff``, above ``max_y_diff`` in y, or has its right keypoint
+    to the RIGHT of the left one with |dx| inside the window (positive u_right, negative depth).  Besides:
+    ``n_non_mutual`` one-sided entries on each side, one idx0 entry past n_right and one idx1 entry past
+    n_left.  ``need_id``: which left keypoints have no track id yet -- "all", "none" or "third" (every
+    third); of those that have one, ``frac_held`` hold a map point (``point_slot`` = the track id) with a
+    position and a state (Good or not).
+
+    Returns a dict: feat_left [n_left, 259], feat_right [n_right, 259], idx0, idx1, track_id, point_slot,
+    points [n_left, 3], state [n_left] uint8, cam, window, Twc [4, 4], next_track_id, kind [n_left] (0 no pair,
+    1 in window, 2 dx small, 3 dx large, 4 dy large, 5 right of left)."""
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy, bf = cam
+    mn, mx, my = stereo_window(bf)
+    n_common = min(n_common, n_left, n_right)
+
+    def feats(n):
+        F = np.zeros((n, 259))
+        F[:, 0] = rng.uniform(0.01, 1.0, n)
+        F[:, 1], F[:, 2] = rng.uniform(120, width - 2, n), rng.uniform(2, height - 2, n)
+        F[:, 3:] = rng.normal(0, 1.0 / 16, (n, 256))
+        return F
+
+    FL, FR = feats(n_left), feats(n_right)
+    idx0, idx1 = np.full(n_left, -1, np.int32), np.full(n_right, -1, np.int32)
+    li, ri = rng.permutation(n_left)[:n_common], rng.permutation(n_right)[:n_common]
+    idx0[li], idx1[ri] = ri, li
+    kind = np.zeros(n_left, np.int32)
+    for c, (i, j) in enumerate(zip(li, ri)):
+        k = (1, 1, 1, 2, 1, 3, 1, 4, 1, 5)[c % 10]
+        dx = {1: rng.uniform(mn + 0.5, min(mx, 110.0)), 2: rng.uniform(0.0, mn - 0.01), 3: mx + rng.uniform(0.5, 9.0),
+              4: rng.uniform(mn + 0.5, 60.0), 5: -rng.uniform(mn + 0.5, 60.0)}[k]
+        if k == 3:
+            FL[i, 1] = mx + 20.0 + rng.uniform(0, 40.0)  # room for a disparity above max_x_diff
+        dy = rng.uniform(my + 0.01, my + 6.0) * rng.choice([-1, 1]) if k == 4 else rng.uniform(-my, my) * 0.9
+        FR[j, 1], FR[j, 2] = FL[i, 1] - dx, FL[i, 2] + dy
+        kind[i] = k
+    free_l, free_r = np.flatnonzero(idx0 < 0), np.flatnonzero(idx1 < 0)
+    if n_right > 0:
+        for i in free_l[:n_non_mutual]:
+            idx0[i] = rng.integers(0, n_right)
+        if len(free_l) > n_non_mutual:
+            idx0[free_l[n_non_mutual]] = n_right + 2
+    if n_left > 0:
+        for j in free_r[:n_non_mutual]:
+            idx1[j] = rng.integers(0, n_left)
+        if len(free_r) > n_non_mutual:
+            idx1[free_r[n_non_mutual]] = n_left + 5
+    # (a one-sided entry may close a pair by chance; kind is recomputed by the restatement, not trusted)
+    ar = np.arange(n_left)
+    need = {"all": np.ones(n_left, bool), "none": np.zeros(n_left, bool), "third": ar % 3 == 0}[need_id]
+    track_id = np.where(need, -1, 7 + 2 * ar).astype(np.int32)
+    held = ~need & (rng.uniform(size=n_left) < frac_held)
+    point_slot = np.where(held, track_id, -1).astype(np.int32)
+    points = np.where(held[:, None], rng.normal(0, 4.0, (n_left, 3)), 0.0)
+    state = np.where(held, np.where(rng.uniform(size=n_left) < 0.8, 1, 2), 0).astype(np.uint8)
+    Twc = _Twc(_rotvec_to_R(rng.normal(0, 0.2, 3)), rng.normal(0, 2.0, 3))
+    return dict(feat_left=FL, feat_right=FR, idx0=idx0, idx1=idx1, track_id=track_id, point_slot=point_slot,
+                points=points, state=state, cam=tuple(float(c) for c in cam), window=(mn, mx, my), Twc=Twc,
+                next_track_id=next_track_id, kind=kind)
+
+
+def raw_sequence(seq: dict, seed: int = 0):
+    """A ``map_sequence`` as tracking would hand it to keyframe insertion: no ready-made landmarks.
+
+    ``new_points`` / ``new_lines`` are dropped.  Each keyframe gets the SuperPoint records of its stereo pair
+    (``feat_left`` from its keypoints, ``feat_right`` with the stereo keypoints' partners at (u_right, y) in a
+    shuffled order plus unmatched ones) and SuperGlue's ``idx0`` / ``idx1``; per keypoint ``track_id`` (-1 when
+    the point was never seen) and ``point_slot`` (the id of the map point it holds, -1 when the map has none
+    yet); per line ``line_track_id`` and ``line_slot``.  The ids are the ones insertion itself hands out when
+    it starts from ``next_track_id`` = ``next_line_track_id`` = 0 and the first keyframe is inserted with
+    ``init`` (MapBuilder::Init: ids for the keypoints with a depth first, map points only for those), which is
+    how ``sequence.run_raw`` drives it; ``point_ids`` / ``line_ids`` map them back to ``seq``'s landmark ids."""
+    rng = np.random.default_rng(seed)
+    cam = seq["camera"]
+    mn, mx, my = stereo_window(cam[4])
+    tid_of, has_mp, lid_of = {}, set(), {}
+    next_tid = 0
+    out = []
+    for k, kf in enumerate(seq["keyframes"]):
+        kp = np.asarray(kf["keypoints"], np.float64).reshape(-1, 3)
+        n = len(kp)
+        st = np.flatnonzero(kp[:, 2] > 0)
+        n_extra = 5
+        FL, FR = np.zeros((n, 259)), np.zeros((len(st) + n_extra, 259))
+        FL[:, 0], FL[:, 1:3] = 0.5, kp[:, :2]
+        perm = rng.permutation(len(FR))
+        idx0, idx1 = np.full(n, -1, np.int32), np.full(len(FR), -1, np.int32)
+        FR[:, 0] = 0.5
+        FR[perm[len(st):], 1:3] = rng.uniform(10, 400, (n_extra, 2))
+        FR[perm[:len(st)], 1], FR[perm[:len(st)], 2] = kp[st, 2], kp[st, 1]
+        idx0[st], idx1[perm[:len(st)]] = perm[:len(st)], st
+        dx = kp[:, 0] - kp[:, 2]
+        pos = (kp[:, 2] > 0) & (dx > mn) & (dx < mx)          # the window keeps it and the depth is positive
+        point_of_kp = {j: i for i, j in kf["point_obs"]}
+        track_id, point_slot = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+        for i in range(n):
+            j = point_of_kp[i]
+            if j in tid_of:
+                track_id[i] = tid_of[j]
+                if j in has_mp:
+                    point_slot[i] = tid_of[j]
+        fresh = np.flatnonzero(track_id < 0)
+        order = np.concatenate([fresh[pos[fresh]], fresh[~pos[fresh]]]) if k == 0 else fresh
+        for i in order:
+            tid_of[point_of_kp[i]] = next_tid
+            next_tid += 1
+        for i in range(n):  # the map points this insertion creates
+            if point_slot[i] < 0 and (k > 0 or pos[i]):
+                has_mp.add(point_of_kp[i])
+        line_of = {j: i for i, j in kf["line_obs"]}
+        nl = len(kf["lines_left"])
+        line_track_id, line_slot = np.full(nl, -1, np.int32), np.full(nl, -1, np.int32)
+        for i in range(nl):
+            if line_of[i] in lid_of:
+                line_track_id[i] = line_slot[i] = lid_of[line_of[i]]
+            else:
+                lid_of[line_of[i]] = len(lid_of)
+        r = {key: kf[key] for key in ("id", "timestamp", "parent_id", "Twc", "lines_left", "lines_right",
+                                      "lines_right_valid", "points_on_lines")}
+        r.update(feat_left=FL, feat_right=FR, idx0=idx0, idx1=idx1, track_id=track_id, point_slot=point_slot,
+                 line_track_id=line_track_id, line_slot=line_slot)
+        out.append(r)
+    return dict(camera=np.array(cam, np.float64), window=(mn, mx, my), gt_Twc=seq["gt_Twc"],
+                timestamps=seq["timestamps"], keyframes=out, point_ids=dict(tid_of), line_ids=dict(lid_of))
+
+
 def line_scene(n_lines: int = 60, n_points: int = 400, seed: int = 0, width: int = 752, height: int = 480,
                disparity: float = 14.0, frag: int = 3, on_line_frac: float = 0.5, noise: float = 0.4):
     """A stereo frame of the line front end: long scene segments observed as
