@@ -10,6 +10,7 @@
  *   FrameOptimization
  *                   include/g2o_optimization/g2o_optimization.h:20-22 -> rspl_frame_*
  *   SolvePnPWithCV  include/g2o_optimization/g2o_optimization.h:24    -> rspl_pnp_*
+ *   Camera          include/camera.h:15-40          -> rspl_rect_*
  * Plain pointers and sizes only; no Eigen / OpenCV / torch types.  Every call
  * returns RSPL_OK (0) or a negative RSPL_E_* code (rspl_last_error() has the
  * text).  Handles are NOT thread-safe: callers serialise, exactly as the
@@ -974,6 +975,74 @@ int rspl_map_insert_keyframe(rspl_map* m, const rspl_map_keyframe* kf, const rsp
 /* a map line's observers in ascending frame id: the line index and Mapline::GetObverserEndpointStatus */
 int rspl_map_get_mapline_observers(const rspl_map* m, int id, int32_t* frames, int32_t* lines,
                                    int32_t* endpoint_status, int cap, int* n_observers);
+
+/* ------------------------------------------------------------------------ */
+/* Stereo rectification: Camera::Camera's maps (src/camera.cc:9-63) and      */
+/* Camera::UndistortImage (src/camera.cc:87-91), which MapBuilder::AddInput  */
+/* runs on both images of every frame (src/map_builder.cc:53-60).  The maps  */
+/* are cv::initUndistortRectifyMap (distortion_type 0, radial-tangential)    */
+/* or cv::fisheye::initUndistortRectifyMap (distortion_type 1) restated, the */
+/* remap is cv::remap(INTER_LINEAR, BORDER_CONSTANT 0) on u8 restated: its   */
+/* fixed-point arithmetic (coordinates rounded half-to-even to 1/32 pixel,   */
+/* integer weights summing to 32768) is followed bit for bit.  OpenCV itself */
+/* is not linked, so parity with it is unpinned at the maps: the 3x3 inverse */
+/* is Gauss-Jordan with partial pivoting where OpenCV uses LU / SVD, and     */
+/* x = _x / _w is a division.  A caller who needs OpenCV's exact maps loads  */
+/* them with rspl_rect_set_maps.                                             */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  double K[9];  /* camera matrix, row-major */
+  double D[8];  /* type 0: k1 k2 p1 p2 k3 k4 k5 k6; type 1: k1 k2 k3 k4 and four zeros.  The struct has no
+                 * room for thin-prism / tilt terms: a caller holding non-zero ones must refuse them */
+  double R[9];  /* rectifying rotation, row-major */
+  double P[12]; /* new projection matrix 3x4, row-major; its left 3x3 is used */
+} rspl_rect_camera;
+
+typedef struct {
+  int height, width;   /* of the raw and of the rectified images; 1..2044 each */
+  int distortion_type; /* 0 radial-tangential, 1 equidistant / fisheye */
+  rspl_rect_camera cam[2]; /* 0 left, 1 right */
+  int max_batch;       /* images per rspl_rect_enqueue_device call, 1..1024 */
+  int device;
+} rspl_rect_config;
+
+typedef struct rspl_rect rspl_rect;
+
+/* Host only, no device: the float maps [H][W] of one camera.  RSPL_E_ARG for a singular P*R, non-finite
+ * parameters, or a fisheye camera with D[4..7] != 0. */
+int rspl_rect_build_maps(const rspl_rect_camera* cam, int distortion_type, int height, int width, float* map_x,
+                         float* map_y);
+/* Host only: the fixed-point table the kernel reads, for n map entries of an H x W source.  ix = floor of
+ * the rounded coordinate in 1/32 pixel, frac = fx | fy << 5.  Coordinates whose taps all lie outside are
+ * clamped: ix = -2 (left of the image, NaN, -inf) or ix = W, with a zero fraction; iy likewise with H. */
+int rspl_rect_debug_fixed(const float* map_x, const float* map_y, size_t n, int height, int width, int16_t* ix,
+                          int16_t* iy, uint16_t* frac);
+/* sizeof of 0: rspl_rect_camera, 1: rspl_rect_config as the library was built (-1 otherwise) */
+int rspl_rect_debug_sizeof(int which);
+/* Measurement hook (tools/bench_rect.py): the copy kernel the handles upload with (copy_kernels.hip) on two
+ * 16-byte aligned device pointers, as the yardstick of what moving an image's bytes costs. */
+int rspl_rect_debug_copy(void* d_dst, const void* d_src, size_t bytes, void* stream);
+
+/* Builds both cameras' maps and the device table once; all device memory is allocated here.  Bad sizes,
+ * capacities and models are refused with RSPL_E_ARG before a device is touched. */
+int rspl_rect_create(const rspl_rect_config* cfg, rspl_rect** out);
+void rspl_rect_destroy(rspl_rect* h);
+/* the float maps [H][W] of camera `cam` (0 / 1) as the handle holds them; set replaces them (maps
+ * exported from OpenCV, for instance) and waits for the handle's earlier work */
+int rspl_rect_get_maps(rspl_rect* h, int cam, float* map_x, float* map_y);
+int rspl_rect_set_maps(rspl_rect* h, int cam, const float* map_x, const float* map_y);
+
+/* Device in, device out, stream-ordered, never waits for the device: raw image b at d_raw + b*raw_pitch
+ * (row stride raw_stride bytes) through the maps of camera cam_index[b] (host array) to d_out + b*out_pitch
+ * (row stride out_stride) -- the layout rspl_sp_infer_device takes.  One launch for the whole batch.
+ * Bytes between width and out_stride are not written.  Overlapping input and output ranges, strides below
+ * the width, pitches below an image and batch > max_batch are RSPL_E_ARG.  stream may be NULL. */
+int rspl_rect_enqueue_device(rspl_rect* h, int batch, const uint8_t* d_raw, size_t raw_stride, size_t raw_pitch,
+                             const int* cam_index, uint8_t* d_out, size_t out_stride, size_t out_pitch,
+                             void* stream);
+/* Camera::UndistortImage: host images in (one row stride for both), rectified host images out. */
+int rspl_rect_pair(rspl_rect* h, const uint8_t* left, const uint8_t* right, size_t stride, uint8_t* left_rect,
+                   uint8_t* right_rect, size_t out_stride);
 
 #ifdef __cplusplus
 }

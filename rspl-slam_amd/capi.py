@@ -51,6 +51,8 @@ EXPORTS = [
     "rspl_track_debug_stage", "rspl_track_keyframe_table",
     "rspl_kf_create", "rspl_kf_destroy", "rspl_kf_enqueue", "rspl_kf_fetch", "rspl_kf_triangulate",
     "rspl_map_insert_keyframe", "rspl_map_get_mapline_observers",
+    "rspl_rect_build_maps", "rspl_rect_debug_fixed", "rspl_rect_debug_sizeof", "rspl_rect_debug_copy", "rspl_rect_create", "rspl_rect_destroy",
+    "rspl_rect_get_maps", "rspl_rect_set_maps", "rspl_rect_enqueue_device", "rspl_rect_pair",
 ]
 
 
@@ -150,6 +152,15 @@ class KfResult(C.Structure):
                 ("n_new_ids", C.c_int), ("n_new_points", C.c_int), ("n_new_good", C.c_int),
                 ("next_track_id", C.c_int), ("u_right", C.c_void_p), ("depth", C.c_void_p), ("track_id", C.c_void_p),
                 ("new_point", C.c_void_p), ("new_position", C.c_void_p)]
+
+
+class RectCamera(C.Structure):
+    _fields_ = [("K", C.c_double * 9), ("D", C.c_double * 8), ("R", C.c_double * 9), ("P", C.c_double * 12)]
+
+
+class RectConfig(C.Structure):
+    _fields_ = [("height", C.c_int), ("width", C.c_int), ("distortion_type", C.c_int), ("cam", RectCamera * 2),
+                ("max_batch", C.c_int), ("device", C.c_int)]
 
 
 class RsplError(RuntimeError):
@@ -274,6 +285,19 @@ def load(path: pathlib.Path = LIB_PATH):
         lib.rspl_kf_enqueue.argtypes = [vp, ip, vp, vp]
         lib.rspl_kf_fetch.argtypes = [vp, vp]
         lib.rspl_kf_triangulate.argtypes = [vp, ip, vp, vp, ip, vp, vp, vp, vp, vp]
+    if hasattr(lib, "rspl_rect_create"):
+        sz = C.c_size_t
+        lib.rspl_rect_build_maps.argtypes = [C.POINTER(RectCamera), ip, ip, ip, vp, vp]
+        lib.rspl_rect_debug_fixed.argtypes = [vp, vp, sz, ip, ip, vp, vp, vp]
+        lib.rspl_rect_debug_sizeof.argtypes = [ip]
+        lib.rspl_rect_debug_copy.argtypes = [vp, vp, sz, vp]
+        lib.rspl_rect_create.argtypes = [C.POINTER(RectConfig), C.POINTER(vp)]
+        lib.rspl_rect_destroy.argtypes = [vp]
+        lib.rspl_rect_destroy.restype = None
+        lib.rspl_rect_get_maps.argtypes = [vp, ip, vp, vp]
+        lib.rspl_rect_set_maps.argtypes = [vp, ip, vp, vp]
+        lib.rspl_rect_enqueue_device.argtypes = [vp, ip, vp, sz, sz, C.POINTER(ip), vp, sz, sz, vp]
+        lib.rspl_rect_pair.argtypes = [vp, vp, vp, sz, vp, vp, sz]
     _lib = lib
     return lib
 
