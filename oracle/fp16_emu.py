@@ -13,7 +13,7 @@ Two parts:
    different orders (numpy's own; input channels permuted and taps reversed): the reference's own
    accumulation-order spread gamma0, measured by tests/test_fp16_emu.py, is the basis of gamma = 4 gamma0.
 
-Where the kernels round (rspl-slam_amd/csrc/sp_kernels.hip, sg_gemm.hip, sg_gnn.hip):
+Where the kernels round (rspl-slam_amd/csrc/sp_conv.hip, sp_heads.hip, sg_gemm.hip, sg_gnn.hip):
   conv3x3_h_kernel     fp16 x, fp16 w; fp32 accumulation; (2x2 max-pool of the accumulators;) + fp32 bias; ReLU;
                        rounded to fp16.
   conv1_res_kernel     pixel (float)(u / 255.0) rounded to fp16; conv1a = one MFMA over the 9 fp16 taps and the

@@ -1,4 +1,4 @@
-// SuperPoint handle: C ABI (include/rspl.h) over the HIP kernels in sp_kernels.hip.
+// SuperPoint handle: C ABI (include/rspl.h) over the HIP kernels in sp_conv.hip, sp_heads.hip, sp_select.hip.
 // Mirrors SuperPoint::build / infer / process_output (src/super_point.cpp:19-319):
 // weights are loaded and re-laid-out once at create; every buffer is carved from
 // one arena sized for max_batch x max_height x max_width.
@@ -263,45 +263,62 @@ int nms_topk(rspl_sp* s, int B, int H, int W, int k, hipStream_t st) {
   return RSPL_OK;
 }
 
-// RSPL_PREC_FP16: the eight 3x3 conv launches (conv1a+1b+pool, conv2a, conv2b+pool, conv3a, conv3b+pool, conv4a,
-// conv4b, convPa | convDa) and the two head launches, each with its whole argument set-up, shared by
-// rspl_sp_infer_device and rspl_sp_debug_layer so that the test hook launches what the product launches.
-constexpr int kH16Convs = 8;
-struct H16Conv { const _Float16* hw; const float* bias; int cin, cout; bool pool; };
+// The encoder schedule (superpoint.py:117-127 and the heads' first convs): eight 3x3 conv stages -- conv1a+1b+pool,
+// conv2a, conv2b+pool, conv3a, conv3b+pool, conv4a, conv4b, convPa | convDa -- with their weights in every
+// precision's layout.  Stage i reads level (H >> shift) x (W >> shift).  One table and one launch function for all
+// three precisions, shared by rspl_sp_infer_device and rspl_sp_debug_layer so that the test hook launches what the
+// product launches.
+constexpr int kConvs = 8;
+struct ConvStage { const float* w; const _Float16 *hw, *lw; const float* bias; int cin, cout; bool pool; int shift; };
 
-H16Conv h16_conv_desc(const rspl_sp* s, int i) {
-  const H16Conv tab[kH16Convs] = {{s->hw1b, s->b1b, 64, 64, true},    {s->hw2a, s->b2a, 64, 64, false},
-                                  {s->hw2b, s->b2b, 64, 64, true},    {s->hw3a, s->b3a, 64, 128, false},
-                                  {s->hw3b, s->b3b, 128, 128, true},  {s->hw4a, s->b4a, 128, 128, false},
-                                  {s->hw4b, s->b4b, 128, 128, false}, {s->hwPD, s->bPD, 128, 512, false}};
+ConvStage conv_stage(const rspl_sp* s, int i) {
+  const ConvStage tab[kConvs] = {
+      {s->w1b, s->hw1b, s->lw1b, s->b1b, 64, 64, true, 0},     {s->w2a, s->hw2a, s->lw2a, s->b2a, 64, 64, false, 1},
+      {s->w2b, s->hw2b, s->lw2b, s->b2b, 64, 64, true, 1},     {s->w3a, s->hw3a, s->lw3a, s->b3a, 64, 128, false, 2},
+      {s->w3b, s->hw3b, s->lw3b, s->b3b, 128, 128, true, 2},   {s->w4a, s->hw4a, s->lw4a, s->b4a, 128, 128, false, 3},
+      {s->w4b, s->hw4b, s->lw4b, s->b4b, 128, 128, false, 3}, {s->wPD, s->hwPD, s->lwPD, s->bPD, 128, 512, false, 3}};
   return tab[i];
 }
-// activations ping-pong actA / actB (conv1 writes actA); convPa | convDa writes the cells
-const _Float16* h16_conv_in(const rspl_sp* s, int i) {
-  return i == 0 ? nullptr : reinterpret_cast<const _Float16*>(i & 1 ? s->actA : s->actB);
+// activations ping-pong actA / actB (conv1 reads the image and writes actA); convPa | convDa writes the cells
+float* conv_in(const rspl_sp* s, int i) { return i == 0 ? nullptr : (i & 1 ? s->actA : s->actB); }
+float* conv_out(const rspl_sp* s, int i) { return i == kConvs - 1 ? s->cells : (i & 1 ? s->actB : s->actA); }
+_Float16* as_half(float* p) { return reinterpret_cast<_Float16*>(p); }
+
+// stage i at precision prec on its own input level H x W; c carries the image / conv1a fields (stage 0 only).
+// The fp16 paths keep their activations in the same fp32-sized buffers; split fp16 holds the hi plane at a
+// buffer's start and the lo plane one plane on (act_pl / cell_pl halves, sized by the full-resolution image).
+hipError_t run_conv(const rspl_sp* s, int i, int prec, sp::ConvArgs c, int H, int W, int B, hipStream_t st,
+                    hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
+  const ConvStage d = conv_stage(s, i);
+  c.H = H; c.W = W; c.cout = d.cout; c.bias = d.bias;
+  if (prec == RSPL_PREC_FP32) {
+    c.in = conv_in(s, i); c.w = d.w; c.out = conv_out(s, i);
+    return sp::conv3x3(c, d.cin, d.pool, i == 0, B, st, t0, t1);
+  }
+  c.hin = as_half(conv_in(s, i)); c.hw = d.hw; c.hout = as_half(conv_out(s, i));
+  if (prec == RSPL_PREC_FP16) return sp::conv3x3_h(c, d.cin, d.pool, i == 0, B, st, t0, t1);
+  const size_t act_pl = ((size_t)B * (H << d.shift) * (W << d.shift)) * 16, cell_pl = (size_t)B * H * W * 512;
+  c.hin_lo = c.hin ? c.hin + act_pl : nullptr; c.hw_lo = d.lw;
+  c.hout_lo = c.hout + (i == kConvs - 1 ? cell_pl : act_pl);
+  return sp::conv3x3_x3(c, d.cin, d.pool, i == 0, B, st, t0, t1);
 }
-_Float16* h16_conv_out(const rspl_sp* s, int i) {
-  return reinterpret_cast<_Float16*>(i == kH16Convs - 1 ? s->cells : (i & 1 ? s->actB : s->actA));
-}
-// stage i at its own input level H x W; c carries the image / conv1a fields (stage 0 only)
-hipError_t h16_conv(const rspl_sp* s, int i, sp::ConvArgs c, int H, int W, int B, hipStream_t st, hipEvent_t t0 = nullptr,
-                    hipEvent_t t1 = nullptr) {
-  const H16Conv d = h16_conv_desc(s, i);
-  c.H = H; c.W = W; c.cout = d.cout; c.hin = h16_conv_in(s, i); c.hw = d.hw; c.bias = d.bias; c.hout = h16_conv_out(s, i);
-  return sp::conv3x3_h(c, d.cin, d.pool, i == 0, false, B, st, t0, t1);
-}
-sp::HeadHArgs h16_head(const rspl_sp* s, int B, int P, int W8) {
+// detector head (superpoint.py:130-135) and descriptor head at the sampled taps + sampling + packing
+// (superpoint.py:159-161, super_point.cpp:206-319) on fp16 MFMA; split fp16 adds the lo planes
+sp::HeadHArgs h16_head(const rspl_sp* s, int prec, int B, int P, int W8) {
   sp::HeadHArgs h{};
-  h.cells = reinterpret_cast<const _Float16*>(s->cells); h.wPb = s->fwPb; h.bPb = s->bPb; h.scores = s->scores;
+  h.cells = as_half(s->cells); h.wPb = s->fwPb; h.bPb = s->bPb; h.scores = s->scores;
   h.B = B; h.P = P; h.W8 = W8;
+  if (prec == RSPL_PREC_FP16X3) { h.cells_lo = h.cells + (size_t)B * P * 512; h.wPb_lo = s->lfwPb; }
   return h;
 }
-sp::TapArgs h16_taps(const rspl_sp* s, double* d_features, int capacity, int32_t* d_counts, int B, int H, int W) {
+sp::TapArgs h16_taps(const rspl_sp* s, int prec, double* d_features, int capacity, int32_t* d_counts, int B, int H,
+                     int W) {
   const int k = s->cfg.max_keypoints;
   sp::TapArgs ta{};
-  ta.cells = reinterpret_cast<const _Float16*>(s->cells); ta.wDb = s->fwDb; ta.bDb = s->bDb;
+  ta.cells = as_half(s->cells); ta.wDb = s->fwDb; ta.bDb = s->bDb;
   ta.sel = s->sel; ta.sel_count = s->sel_count; ta.sel_stride = kCandCap; ta.per_image = (k > 0 ? k : kCandCap);
   ta.nms = s->scores; ta.features = d_features; ta.feat_cap = capacity; ta.counts = d_counts; ta.B = B; ta.H = H; ta.W = W;
+  if (prec == RSPL_PREC_FP16X3) { ta.cells_lo = ta.cells + (size_t)B * (H / 8) * (W / 8) * 512; ta.wDb_lo = s->lfwDb; }
   return ta;
 }
 }  // namespace
@@ -314,11 +331,10 @@ extern "C" int rspl_sp_infer_device(rspl_sp* s, const uint8_t* d_images, int B, 
   RSPL_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && H <= s->cfg.max_height && W <= s->cfg.max_width,
                  "image %dx%d: must be multiples of 8 within %dx%d", H, W, s->cfg.max_height, s->cfg.max_width);
   RSPL_CHECK_ARG(stride >= W, "stride < width");
-  const int k = s->cfg.max_keypoints;
+  const int k = s->cfg.max_keypoints, prec = s->cfg.precision;
   RSPL_CHECK_ARG(capacity >= (k > 0 ? k : kCandCap), "capacity %d below max_keypoints", capacity);
   hipStream_t st = stream_ ? (hipStream_t)stream_ : s->stream;
-  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8;
-  const int P = H8 * W8;
+  const int W8 = W / 8, P = (H / 8) * W8;
   using namespace sp;
   ConvArgs c{};
   c.img = d_images;
@@ -327,110 +343,35 @@ extern "C" int rspl_sp_infer_device(rspl_sp* s, const uint8_t* d_images, int B, 
   c.lut = s->lut;
   c.w1a = s->w1a;
   c.b1a = s->b1a;
-  // encoder (superpoint.py:117-127)
-  if (s->cfg.precision == RSPL_PREC_FP16X3) {
-    // split fp16: every activation a pair of fp16 planes (hi at the buffer's start, lo half a buffer on: the
-    // fp32-sized arenas hold both), three MFMA products per step (sp_kernels.hip conv3x3_x3_kernel)
-    const size_t act_pl = (size_t)B * H * W * 16, cell_pl = (size_t)B * P * 512;  // halves per lo-plane offset
-    _Float16* hA = reinterpret_cast<_Float16*>(s->actA);
-    _Float16* hB = reinterpret_cast<_Float16*>(s->actB);
-    _Float16* hC = reinterpret_cast<_Float16*>(s->cells);
-    auto layer = [&](const _Float16* in, const _Float16* hw, const _Float16* lw, const float* bias, _Float16* out) {
-      c.hin = in; c.hin_lo = in ? in + act_pl : nullptr; c.hw = hw; c.hw_lo = lw; c.bias = bias;
-      c.hout = out; c.hout_lo = out + (out == hC ? cell_pl : act_pl);
-    };
-    c.H = H; c.W = W; c.cout = 64;
-    layer(nullptr, s->hw1b, s->lw1b, s->b1b, hA);
-    RSPL_HIP(conv3x3_x3(c, 64, true, true, B, st, s->timer.slot(0), s->timer.slot(1)));  // conv1a+1b+pool
-    c.H = H2; c.W = W2; c.cout = 64; layer(hA, s->hw2a, s->lw2a, s->b2a, hB);
-    RSPL_HIP(conv3x3_x3(c, 64, false, false, B, st));                                   // conv2a
-    layer(hB, s->hw2b, s->lw2b, s->b2b, hA);
-    RSPL_HIP(conv3x3_x3(c, 64, true, false, B, st));                                    // conv2b+pool
-    c.H = H4; c.W = W4; c.cout = 128; layer(hA, s->hw3a, s->lw3a, s->b3a, hB);
-    RSPL_HIP(conv3x3_x3(c, 64, false, false, B, st));                                   // conv3a
-    layer(hB, s->hw3b, s->lw3b, s->b3b, hA);
-    RSPL_HIP(conv3x3_x3(c, 128, true, false, B, st));                                   // conv3b+pool
-    c.H = H8; c.W = W8; layer(hA, s->hw4a, s->lw4a, s->b4a, hB);
-    RSPL_HIP(conv3x3_x3(c, 128, false, false, B, st));                                  // conv4a
-    layer(hB, s->hw4b, s->lw4b, s->b4b, hA);
-    RSPL_HIP(conv3x3_x3(c, 128, false, false, B, st));                                  // conv4b
-    s->timer.mark(2, st);
-    c.cout = 512; layer(hA, s->hwPD, s->lwPD, s->bPD, hC);
-    RSPL_HIP(conv3x3_x3(c, 128, false, false, B, st));                                  // convPa | convDa
-    s->timer.mark(3, st);
-    HeadHArgs h{};
-    h.cells = hC; h.cells_lo = hC + cell_pl; h.wPb = s->fwPb; h.wPb_lo = s->lfwPb; h.bPb = s->bPb;
-    h.scores = s->scores; h.B = B; h.P = P; h.W8 = W8;
-    RSPL_HIP(det_head_h(h, true, st));
-    s->timer.mark(4, st);
-    if (int rc = nms_topk(s, B, H, W, k, st)) return rc;
-    s->timer.mark(6, st);
-    TapArgs ta{};
-    ta.cells = hC; ta.cells_lo = hC + cell_pl; ta.wDb = s->fwDb; ta.wDb_lo = s->lfwDb; ta.bDb = s->bDb;
-    ta.sel = s->sel; ta.sel_count = s->sel_count; ta.sel_stride = kCandCap; ta.per_image = (k > 0 ? k : kCandCap);
-    ta.nms = s->scores; ta.features = d_features; ta.feat_cap = capacity; ta.counts = d_counts; ta.B = B; ta.H = H; ta.W = W;
-    RSPL_HIP(sample_taps_h(ta, true, st));
-    s->timer.mark(7, st);
-    s->timer.end_call();
-    s->last_B = B; s->last_H = H; s->last_W = W;
-    return RSPL_OK;
-  } else if (s->cfg.precision == RSPL_PREC_FP16) {  // the reference's TensorRT kFP16 engine (super_point.cpp:98)
-    // stage 0 = the fused conv1 kernel exactly (events stamped by the launch itself)
-    const int lh[kH16Convs] = {H, H2, H2, H4, H4, H8, H8, H8}, lw[kH16Convs] = {W, W2, W2, W4, W4, W8, W8, W8};
-    for (int i = 0; i < kH16Convs; i++) {  // conv1a+1b+pool, conv2a .. conv4b, convPa | convDa (fp16 out)
-      RSPL_HIP(h16_conv(s, i, c, lh[i], lw[i], B, st, i ? nullptr : s->timer.slot(0), i ? nullptr : s->timer.slot(1)));
-      if (i == kH16Convs - 2) s->timer.mark(2, st);
-    }
-    s->timer.mark(3, st);
-    // detector head (superpoint.py:130-135) on fp16 MFMA
-    RSPL_HIP(det_head_h(h16_head(s, B, P, W8), false, st));
-    s->timer.mark(4, st);
-    if (int rc = nms_topk(s, B, H, W, k, st)) return rc;
-    // descriptor head at the sampled taps + sampling + packing (superpoint.py:159-161,
-    // super_point.cpp:206-319)
-    s->timer.mark(6, st);
-    RSPL_HIP(sample_taps_h(h16_taps(s, d_features, capacity, d_counts, B, H, W), false, st));
-    s->timer.mark(7, st);
-    s->timer.end_call();
-    s->last_B = B; s->last_H = H; s->last_W = W;
-    return RSPL_OK;
-  } else {
-    // encoder (superpoint.py:117-127)
-    c.H = H; c.W = W; c.cout = 64; c.w = s->w1b; c.bias = s->b1b; c.out = s->actA;
-    RSPL_HIP(conv3x3(c, 64, true, true, B, st, s->timer.slot(0), s->timer.slot(1)));  // conv1a+1b+pool
-    c.H = H2; c.W = W2; c.cout = 64; c.in = s->actA; c.w = s->w2a; c.bias = s->b2a; c.out = s->actB;
-    RSPL_HIP(conv3x3(c, 64, false, false, B, st));                             // conv2a
-    c.in = s->actB; c.w = s->w2b; c.bias = s->b2b; c.out = s->actA;
-    RSPL_HIP(conv3x3(c, 64, true, false, B, st));                              // conv2b+pool
-    c.H = H4; c.W = W4; c.cout = 128; c.in = s->actA; c.w = s->w3a; c.bias = s->b3a; c.out = s->actB;
-    RSPL_HIP(conv3x3(c, 64, false, false, B, st));                             // conv3a
-    c.in = s->actB; c.w = s->w3b; c.bias = s->b3b; c.out = s->actA;
-    RSPL_HIP(conv3x3(c, 128, true, false, B, st));                             // conv3b+pool
-    c.H = H8; c.W = W8; c.in = s->actA; c.w = s->w4a; c.bias = s->b4a; c.out = s->actB;
-    RSPL_HIP(conv3x3(c, 128, false, false, B, st));                            // conv4a
-    c.in = s->actB; c.w = s->w4b; c.bias = s->b4b; c.out = s->actA;
-    RSPL_HIP(conv3x3(c, 128, false, false, B, st));                            // conv4b
-    s->timer.mark(2, st);
-    c.cout = 512; c.in = s->actA; c.w = s->wPD; c.bias = s->bPD; c.out = s->cells;
-    RSPL_HIP(conv3x3(c, 128, false, false, B, st));                            // convPa | convDa
+  // encoder + convPa | convDa; stage 0 = the fused conv1 kernel exactly (events stamped by the launch itself)
+  for (int i = 0; i < kConvs; i++) {
+    const int sh = conv_stage(s, i).shift;
+    RSPL_HIP(run_conv(s, i, prec, c, H >> sh, W >> sh, B, st, i ? nullptr : s->timer.slot(0), i ? nullptr : s->timer.slot(1)));
+    if (i == kConvs - 2) s->timer.mark(2, st);
   }
   s->timer.mark(3, st);
-  // heads (superpoint.py:130-135, 159-161)
-  HeadArgs h{};
-  h.in = s->cells; h.B = B; h.P = P; h.W8 = W8;
-  h.w = s->wPb; h.bias = s->bPb; h.scores = s->scores;
-  RSPL_HIP(heads(h, 0, st));
-  h.w = s->wDb; h.bias = s->bDb; h.desc = s->desc;
-  RSPL_HIP(heads(h, 1, st));
+  if (prec == RSPL_PREC_FP32) {  // heads (superpoint.py:130-135, 159-161): dense scores and descriptors
+    HeadArgs h{};
+    h.in = s->cells; h.B = B; h.P = P; h.W8 = W8;
+    h.w = s->wPb; h.bias = s->bPb; h.scores = s->scores;
+    RSPL_HIP(heads(h, 0, st));
+    h.w = s->wDb; h.bias = s->bDb; h.desc = s->desc;
+    RSPL_HIP(heads(h, 1, st));
+  } else {  // RSPL_PREC_FP16: the reference's TensorRT kFP16 engine (super_point.cpp:98); RSPL_PREC_FP16X3
+    RSPL_HIP(det_head_h(h16_head(s, prec, B, P, W8), prec == RSPL_PREC_FP16X3, st));
+  }
   s->timer.mark(4, st);
   if (int rc = nms_topk(s, B, H, W, k, st)) return rc;
-  // descriptor sampling + packing (super_point.cpp:206-319)
   s->timer.mark(6, st);
-  SampleArgs sa{};
-  sa.sel = s->sel; sa.sel_count = s->sel_count; sa.sel_stride = kCandCap; sa.per_image = (k > 0 ? k : kCandCap);
-  sa.nms = s->scores; sa.desc = s->desc; sa.features = d_features; sa.feat_cap = capacity;
-  sa.counts = d_counts; sa.B = B; sa.H = H; sa.W = W;
-  RSPL_HIP(sample(sa, st));
+  if (prec == RSPL_PREC_FP32) {  // descriptor sampling + packing (super_point.cpp:206-319)
+    SampleArgs sa{};
+    sa.sel = s->sel; sa.sel_count = s->sel_count; sa.sel_stride = kCandCap; sa.per_image = (k > 0 ? k : kCandCap);
+    sa.nms = s->scores; sa.desc = s->desc; sa.features = d_features; sa.feat_cap = capacity;
+    sa.counts = d_counts; sa.B = B; sa.H = H; sa.W = W;
+    RSPL_HIP(sample(sa, st));
+  } else {
+    RSPL_HIP(sample_taps_h(h16_taps(s, prec, d_features, capacity, d_counts, B, H, W), prec == RSPL_PREC_FP16X3, st));
+  }
   s->timer.mark(7, st);
   s->timer.end_call();
   s->last_B = B; s->last_H = H; s->last_W = W;
@@ -554,7 +495,7 @@ extern "C" int rspl_sp_debug_layer(rspl_sp* s, int stage, int B, int H, int W, c
     return e;
   };
   if (stage <= RSPL_SP_LAYER_CONVPD) {
-    const H16Conv d = h16_conv_desc(s, stage);
+    const ConvStage d = conv_stage(s, stage);
     RSPL_CHECK_ARG(!d.pool || (H % 2 == 0 && W % 2 == 0), "a pooled stage needs even H, W");
     const size_t n_in = (size_t)B * H * W * (stage ? d.cin : 1);
     const size_t n_out = (size_t)B * (d.pool ? (H / 2) * (W / 2) : H * W) * d.cout;
@@ -565,26 +506,26 @@ extern "C" int rspl_sp_debug_layer(rspl_sp* s, int stage, int B, int H, int W, c
       RSPL_HIP(hipMemcpy(s->image, in, n_in, hipMemcpyHostToDevice));
       c.img = s->image; c.img_stride = W; c.img_pitch = (size_t)H * W; c.lut = s->lut; c.w1a = s->w1a; c.b1a = s->b1a;
     } else {
-      RSPL_HIP(up_half(static_cast<const float*>(in), const_cast<_Float16*>(h16_conv_in(s, stage)), n_in));
+      RSPL_HIP(up_half(static_cast<const float*>(in), as_half(conv_in(s, stage)), n_in));
     }
-    RSPL_HIP(h16_conv(s, stage, c, H, W, B, st));
+    RSPL_HIP(run_conv(s, stage, RSPL_PREC_FP16, c, H, W, B, st));
     RSPL_HIP(hipStreamSynchronize(st));
-    RSPL_HIP(down_half(h16_conv_out(s, stage), static_cast<float*>(out), n_out));
+    RSPL_HIP(down_half(as_half(conv_out(s, stage)), static_cast<float*>(out), n_out));
     return RSPL_OK;
   }
   // the heads: H x W is the cell grid
   const int P = H * W;
   RSPL_CHECK_ARG((size_t)B * P * 512 <= cell_cap && (size_t)B * P * 64 <= mHW, "cell grid %dx%d x %d exceeds the arena", H,
                  W, B);
-  RSPL_HIP(up_half(static_cast<const float*>(in), reinterpret_cast<_Float16*>(s->cells), (size_t)B * P * 512));
+  RSPL_HIP(up_half(static_cast<const float*>(in), as_half(s->cells), (size_t)B * P * 512));
   if (stage == RSPL_SP_LAYER_DET_HEAD) {
-    RSPL_HIP(sp::det_head_h(h16_head(s, B, P, W), false, st));
+    RSPL_HIP(sp::det_head_h(h16_head(s, RSPL_PREC_FP16, B, P, W), false, st));
     RSPL_HIP(hipStreamSynchronize(st));
     RSPL_HIP(hipMemcpy(out, s->scores, sizeof(float) * B * P * 64, hipMemcpyDeviceToHost));
     return RSPL_OK;
   }
   RSPL_CHECK_ARG(scores && kp && kp_counts && counts_out && kp_stride >= 1, "taps: NULL argument");
-  const sp::TapArgs ta = h16_taps(s, s->features, s->feat_cap, s->counts, B, 8 * H, 8 * W);
+  const sp::TapArgs ta = h16_taps(s, RSPL_PREC_FP16, s->features, s->feat_cap, s->counts, B, 8 * H, 8 * W);
   for (int b = 0; b < B; b++) {
     RSPL_CHECK_ARG(kp_counts[b] >= 0 && kp_counts[b] <= kp_stride && kp_counts[b] <= ta.per_image,
                    "taps: count %d outside [0, %d]", kp_counts[b], std::min(kp_stride, ta.per_image));

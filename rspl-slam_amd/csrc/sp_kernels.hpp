@@ -3,6 +3,7 @@
 
 #include <cstdint>
 
+// Host-facing interface of the SuperPoint units: sp_conv.hip, sp_heads.hip, sp_select.hip.
 namespace rspl {
 namespace sp {
 
@@ -24,7 +25,7 @@ struct ConvArgs {
   // fp16 NHWC activations and weights, fp32 accumulation and epilogue
   const _Float16* hin;   // NHWC [B][H][W][Cin]
   const _Float16* hw;    // [9][Cout][Cin]
-  _Float16* hout;        // NHWC [B][H(/2)][W(/2)][Cout] (or `out` in fp32 for the heads)
+  _Float16* hout;        // NHWC [B][H(/2)][W(/2)][Cout]
   // RSPL_PREC_FP16X3 (split fp16, conv3x3_x3): the lo planes of hin / hw / hout (v = hi + lo)
   const _Float16* hin_lo;
   const _Float16* hw_lo;
@@ -107,10 +108,10 @@ struct SampleArgs {
 
 hipError_t conv3x3(const ConvArgs& a, int cin, bool pool, bool fuse1a, int B, hipStream_t s, hipEvent_t t0 = nullptr,
                    hipEvent_t t1 = nullptr);
-// fp16 MFMA (v_mfma_f32_32x32x16_f16) variant; out_f32 writes `out` (fp32) instead of `hout`
+// fp16 MFMA (v_mfma_f32_32x32x16_f16) variant
 // t0 / t1 (may be null): events stamped with the fused conv1 kernel's own start / end
-hipError_t conv3x3_h(const ConvArgs& a, int cin, bool pool, bool fuse1a, bool out_f32, int B, hipStream_t s,
-                     hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+hipError_t conv3x3_h(const ConvArgs& a, int cin, bool pool, bool fuse1a, int B, hipStream_t s, hipEvent_t t0 = nullptr,
+                     hipEvent_t t1 = nullptr);
 // split-fp16 (RSPL_PREC_FP16X3) variant: hi + lo planes, three MFMA products per k-step
 hipError_t conv3x3_x3(const ConvArgs& a, int cin, bool pool, bool fuse1a, int B, hipStream_t s,
                       hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);

@@ -104,6 +104,57 @@ def test_sp_batched_device_path(pkg, weight_blobs):
         compare_features(F[b, :cnt[b]].T, G)
 
 
+_PARTIAL_SHAPES = [(24, 40), (136, 264)]
+_PARTIAL_K = 400
+
+
+@pytest.fixture(scope="module")
+def partial_oracle(pkg, weight_blobs):
+    """(H, W) -> (the two images, per image (scores, desc, features)): one oracle pass shared by both precisions"""
+    ref = {}
+    for H, W in _PARTIAL_SHAPES:
+        imgs = pkg.synthetic.stereo_pair(H, W, seed=3)
+        per = []
+        for img in imgs:
+            s, d = oracle.sp_forward(weight_blobs[0], post.image_to_input(img))
+            per.append((s, d, post.sp_postprocess(s, d, 0.004, 4, _PARTIAL_K)))
+        ref[(H, W)] = (imgs, per)
+    return ref
+
+
+@pytest.mark.parametrize("H,W", _PARTIAL_SHAPES)
+@pytest.mark.parametrize("precision", ["fp32", "fp16x3"])
+def test_sp_partial_tiles_batch2(pkg, weight_blobs, partial_oracle, precision, H, W):
+    """A batch of two whose levels are partial tiles in both axes, on the fp32 and split-fp16 paths (the conv
+    kernels of both address their tiles and bound their stores the same way): 24x40 gives levels 12x20, 6x10
+    and 3x5 (the TH = 8 instances), 136x264 gives 68x132, 34x66 and 17x33 (the TH = 16 pooled instances and the
+    cell grid).  Default threshold 0.004 and border 4; the oracle alone yields 12 and 11 keypoints at 24x40 and
+    400 each at 136x264, so no comparison is of empty sets."""
+    from rspl_slam_amd import capi
+    k = _PARTIAL_K
+    imgs, ref = partial_oracle[(H, W)]
+    prec = {"fp32": capi.RSPL_PREC_FP32, "fp16x3": capi.RSPL_PREC_FP16X3}[precision]
+    sp = pkg.SuperPoint(pkg.SuperPointConfig(max_keypoints=k, keypoint_threshold=0.004, remove_borders=4,
+                                             weights=weight_blobs[0], max_height=H, max_width=W, max_batch=2,
+                                             precision=prec))
+    assert sp.build(), sp.error
+    st = capi.Stream()
+    dimgs = capi.DeviceBuffer(2 * H * W).upload(np.stack(imgs))
+    feats = capi.DeviceBuffer(2 * k * 259 * 8)
+    counts = capi.DeviceBuffer(2 * 4)
+    sp.infer_device(dimgs.ptr, 2, H, W, W, H * W, feats.ptr, k, counts.ptr, st.handle)
+    st.synchronize()
+    F = feats.download((2, k, 259), np.float64)
+    cnt = counts.download((2,), np.int32)
+    for b, (s, d, G) in enumerate(ref):
+        assert G.shape[1] > 0
+        compare_features(F[b, :cnt[b]].T, G)
+        if precision == "fp32":
+            sm, dm = sp.debug_maps(b, H, W)
+            np.testing.assert_allclose(dm, d, rtol=1e-3, atol=1e-5)
+            np.testing.assert_allclose(sm, s, rtol=1e-3, atol=1e-5)  # the oracle's scores are post-NMS
+
+
 def test_sp_fp16_vs_reference(pkg, golden, weight_blobs):
     """RSPL_PREC_FP16 (the reference's TensorRT kFP16 engine, src/super_point.cpp:98) vs the fp32
     reference outputs, at SURVEY §8c's fp16 acceptance bar: keypoint-set overlap >= 99 % and

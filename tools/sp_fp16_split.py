@@ -2,7 +2,7 @@
 verdict): every layer chosen to be "fp16" takes its input activations and weights rounded to fp16, computes
 in fp32 (an fp16 x fp16 product is exact in fp32, so this is the MFMA's arithmetic up to the accumulation
 order) and, when the NEXT layer is fp16 too, its output is stored rounded to fp16 -- exactly the roundings of
-librspl's fp16 kernels (sp_kernels.hip: conv3x3_h_kernel / conv1_res_kernel / det_head_h_kernel /
+librspl's fp16 kernels (sp_conv.hip, sp_heads.hip: conv3x3_h_kernel / conv1_res_kernel / det_head_h_kernel /
 sample_taps_h_kernel).  An fp32 layer is the parity path's arithmetic.  The post-processing (NMS, threshold,
 borders, top-k, fp64 sampling) is the oracle's (oracle/post.py), i.e. the reference's.  The emulation itself
 is oracle/fp16_emu.py's Emu.
