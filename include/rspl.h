@@ -400,6 +400,24 @@ int rspl_ba_trace(rspl_ba* ba, double* out, int cap, int* n);
 int rspl_ba_debug_stage(const rspl_ba_problem* problem, int par_edges, int rank, int nranks, int* n_local,
                         int* lm_off, int8_t* etype, int* epose, int* elm, int* ecam, int* gmap, int* lpose,
                         double* eobs);
+/* Test hooks (host only, no device): the Schur chunk geometry (ba::chunk_plan) of a window of n_landmarks
+ * landmarks (points + lines) and n_poses optimised poses in a handle created for max_landmarks / max_poses.
+ * chunks: Schur chunks of the window, grid: workgroups of the chunk kernel's launch (idle slots included),
+ * ue_bpr: update workgroups per range when they follow the chunks' XCDs (else 0), slots: chunks the handle's
+ * buffers hold.
+ * rspl_ba_debug_chunk_geometry: per chunk c < chunks, chunks[6 c ...] = {pose pair, first landmark, end landmark
+ * (clamped to n_landmarks), first chunk of its pose pair, end chunk of its pose pair, nominal end landmark};
+ * order[vb] for vb < grid: the chunk that workgroup vb of the launch runs, -1 for an idle slot, -2 if the launch
+ * order's geometry of that chunk disagrees with chunks[]. */
+typedef struct {
+  int32_t nchk, lmchunk, dsub, lmsub;
+  int32_t chunks, grid, ue_bpr;
+  int64_t slots;
+} rspl_ba_chunk_plan;
+int rspl_ba_debug_chunk_plan(int n_landmarks, int n_poses, int max_landmarks, int max_poses,
+                             rspl_ba_chunk_plan* out);
+int rspl_ba_debug_chunk_geometry(int n_landmarks, int n_poses, int max_landmarks, int max_poses, int32_t* chunks,
+                                 int32_t* order);
 
 /* ------------------------------------------------------------------------ */
 /* Landmark-sharded local BA: nranks handles -- one per  */

@@ -40,6 +40,7 @@ EXPORTS = [
     "rspl_pm_match",
     "rspl_ba_create", "rspl_ba_local", "rspl_ba_submit", "rspl_ba_join", "rspl_ba_destroy", "rspl_ba_use_reserved_cus", "rspl_ba_kernel_timing",
     "rspl_ba_kernel_times", "rspl_ba_trace", "rspl_ba_set_line_jacobian", "rspl_ba_debug_stage",
+    "rspl_ba_debug_chunk_plan", "rspl_ba_debug_chunk_geometry",
     "rspl_frame_create", "rspl_frame_optimize", "rspl_frame_destroy",
     "rspl_ba_set_shard", "rspl_comm_unique_id", "rspl_comm_create", "rspl_comm_allreduce_sum", "rspl_comm_destroy",
     "rspl_ba_set_comm", "rspl_group_create", "rspl_group_destroy", "rspl_ba_set_group",
@@ -71,6 +72,11 @@ class SgConfig(C.Structure):
 class SgSinkhornPlan(C.Structure):
     _fields_ = [("kind", C.c_int32), ("groups", C.c_int32), ("rows_per_wave", C.c_int32), ("reserved", C.c_int32),
                 ("ug_granules", C.c_uint64), ("vg_granules", C.c_uint64)]
+
+
+class BaChunkPlan(C.Structure):
+    _fields_ = [("nchk", C.c_int32), ("lmchunk", C.c_int32), ("dsub", C.c_int32), ("lmsub", C.c_int32),
+                ("chunks", C.c_int32), ("grid", C.c_int32), ("ue_bpr", C.c_int32), ("slots", C.c_int64)]
 
 
 class DMatch(C.Structure):
@@ -243,6 +249,9 @@ def load(path: pathlib.Path = LIB_PATH):
         lib.rspl_ba_destroy.argtypes = [vp]
         lib.rspl_ba_destroy.restype = None
         lib.rspl_ba_debug_stage.argtypes = [vp, ip, ip, ip] + [vp] * 9
+    if hasattr(lib, "rspl_ba_debug_chunk_plan"):  # (absent from older builds used as A/B baselines)
+        lib.rspl_ba_debug_chunk_plan.argtypes = [ip, ip, ip, ip, C.POINTER(BaChunkPlan)]
+        lib.rspl_ba_debug_chunk_geometry.argtypes = [ip, ip, ip, ip, vp, vp]
     if hasattr(lib, "rspl_ba_trace"):  # (absent from older builds used as A/B baselines)
         lib.rspl_ba_trace.argtypes = [vp, C.POINTER(C.c_double), ip, C.POINTER(ip)]
         lib.rspl_ba_set_line_jacobian.argtypes = [vp, ip]

@@ -269,13 +269,13 @@ void carve(F& ar, rspl_ba* b) {
   // partial2: scale partials, and the pose-diagonal partials (K x E/256 x 6) of the lambda init
   take(b->partial2, std::max(std::max((size_t)b->maxV / 256, nblk) + 1026, K * (E / 256 + 1) * 6));
   take(b->lm_ctr, nl);
-  const size_t npairs = K * (K + 1) / 2, nchk = std::max<size_t>((NL + ba::kLmChunk - 1) / ba::kLmChunk, 1);
+  const size_t npairs = K * (K + 1) / 2, slots = ba::chunk_slots_for((int)NL, (int)K);
   // pair_ctr: + the solve ticket
-  take(b->chunk, npairs * nchk * 48); take(b->pairfin, npairs * 48 + 8); take(b->pair_ctr, npairs + 1);
+  take(b->chunk, slots * 48); take(b->pairfin, npairs * 48 + 8); take(b->pair_ctr, npairs + 1);
   take(b->red, 6 * K + kMaxRanks + 8);
   take(b->lmctl, 2);
-  take(b->pp_cnt, npairs * nchk); take(b->pp_off, npairs * nchk + 1);
-  b->chunk_slots = npairs * nchk;
+  take(b->pp_cnt, slots); take(b->pp_off, slots + 1);
+  b->chunk_slots = slots;
 }
 
 // Staging slots are allocated at create for the handle's capacities (stage_bytes), so in use this never
@@ -1157,6 +1157,86 @@ extern "C" int rspl_ba_join(rspl_ba* b, long long* calls, long long* iterations,
   return rc;
 }
 
+namespace rspl {
+namespace ba {
+// Schur chunks: ranges of kLmChunk landmarks per pose pair while the chunk waves fit one dispatch round (C3: 45 pairs
+// x 16 ranges); with many pose pairs (C5: K = 29, 435 pairs) fewer, wider ranges -- each wave then walks more
+// passes, but the chip runs them in one round instead of ~17.
+// Wide windows (K > the single-wave solve's, fewer than 8 ranges per pair): a diagonal pose pair walks about
+// (K - 1) / (obs - 1) times an off-diagonal pair's edge pairs (C5: ~970 vs ~170 per range) and set the chunk phase
+// alone -- its ranges are cut into kDiagSub sub-chunks (the off-diagonal pairs keep theirs).  On the single-wave
+// windows the diagonal pairs' ranges stay whole and their chunks are launched first (chunk_at).
+ChunkPlan chunk_plan(int nL, int K, size_t chunk_slots) {
+  constexpr int kDiagSub = 8;
+  const int npairs = K * (K + 1) / 2;
+  ChunkPlan p{};
+  p.nchk = std::max(1, std::min((nL + kLmChunk - 1) / kLmChunk, kChunkWaves / std::max(npairs, 1)));
+  p.lmchunk = std::max(kLmChunk, ((nL + p.nchk - 1) / p.nchk + 63) / 64 * 64);
+  p.nchk = std::max((nL + p.lmchunk - 1) / p.lmchunk, 1);
+  p.dsub = 1;
+  p.lmsub = p.lmchunk;
+  if (!wave_path(K) && p.nchk < 8 && (size_t)p.nchk * (npairs + (kDiagSub - 1) * K) <= chunk_slots) {
+    p.dsub = kDiagSub;
+    p.lmsub = ((p.lmchunk + kDiagSub - 1) / kDiagSub + 63) / 64 * 64;
+  }
+  return p;
+}
+
+// chunks a handle of these capacities holds: ranges of kLmChunk for every pose pair (a window's plan without
+// diagonal sub-chunks never has more; the sub-chunks are taken only where they fit)
+size_t chunk_slots_for(int max_landmarks, int max_poses) {
+  const size_t NL = std::max(max_landmarks, 0), K = std::max(max_poses, 0);
+  return K * (K + 1) / 2 * std::max<size_t>((NL + kLmChunk - 1) / kLmChunk, 1);
+}
+}  // namespace ba
+}  // namespace rspl
+
+extern "C" int rspl_ba_debug_chunk_plan(int n_landmarks, int n_poses, int max_landmarks, int max_poses,
+                                        rspl_ba_chunk_plan* out) {
+  RSPL_CHECK_ARG(out, "rspl_ba_debug_chunk_plan: NULL argument");
+  RSPL_CHECK_ARG(n_landmarks >= 0 && n_poses >= 0 && max_landmarks >= n_landmarks && max_poses >= n_poses,
+                 "rspl_ba_debug_chunk_plan: bad sizes");
+  const size_t slots = ba::chunk_slots_for(max_landmarks, max_poses);
+  const ba::ChunkPlan p = ba::chunk_plan(n_landmarks, n_poses, slots);
+  ba::Active A{};
+  A.nchk = p.nchk; A.lmchunk = p.lmchunk; A.dsub = p.dsub; A.lmsub = p.lmsub;
+  A.K = n_poses;
+  A.npairs = n_poses * (n_poses + 1) / 2;
+  A.nL = n_landmarks;
+  ba::set_update_geometry(A);
+  *out = rspl_ba_chunk_plan{p.nchk, p.lmchunk, p.dsub, p.lmsub, ba::chunk_count(A), ba::chunk_grid(A), A.ue_bpr,
+                            (int64_t)slots};
+  return RSPL_OK;
+}
+
+extern "C" int rspl_ba_debug_chunk_geometry(int n_landmarks, int n_poses, int max_landmarks, int max_poses,
+                                            int32_t* chunks, int32_t* order) {
+  RSPL_CHECK_ARG(chunks && order, "rspl_ba_debug_chunk_geometry: NULL argument");
+  rspl_ba_chunk_plan pl;
+  if (const int rc = rspl_ba_debug_chunk_plan(n_landmarks, n_poses, max_landmarks, max_poses, &pl)) return rc;
+  ba::Active A{};
+  A.nchk = pl.nchk; A.lmchunk = pl.lmchunk; A.dsub = pl.dsub; A.lmsub = pl.lmsub;
+  A.K = n_poses;
+  A.npairs = n_poses * (n_poses + 1) / 2;
+  A.nL = n_landmarks;
+  for (int c = 0; c < pl.chunks; c++) {  // the geometry the pair lists are built from (pair_scan)
+    const ba::ChunkGeo q = ba::chunk_geo(A, c);
+    const int32_t row[6] = {q.pr, q.g0, q.g1, q.c0, q.c1, q.gend};
+    std::copy(row, row + 6, chunks + 6 * c);
+  }
+  for (int vb = 0; vb < pl.grid; vb++) {  // the launch order (pair_chunk); the chunk's own geometry must agree
+    int c = -1;
+    ba::ChunkGeo q;
+    order[vb] = -1;
+    if (!ba::chunk_at(A, vb, c, q)) continue;
+    const ba::ChunkGeo r = ba::chunk_geo(A, c);
+    const bool same = q.pr == r.pr && q.lb == r.lb && q.g0 == r.g0 && q.g1 == r.g1 && q.gend == r.gend &&
+                      q.c0 == r.c0 && q.c1 == r.c1;
+    order[vb] = same ? c : -2;
+  }
+  return RSPL_OK;
+}
+
 extern "C" int rspl_ba_debug_stage(const rspl_ba_problem* pr, int par_edges, int rank, int nranks, int* n_local,
                                    int* lm_off, int8_t* etype, int* epose, int* elm, int* ecam, int* gmap,
                                    int* lpose, double* eobs) {
@@ -1398,25 +1478,12 @@ int run_call(rspl_ba* b, const ba::StagedCall& c, const rspl_ba_problem* pr, rsp
   A.lm_act = reinterpret_cast<const uint8_t*>(cb + cl.lm_act);
   A.pairs = reinterpret_cast<const int*>(cb + cl.pairs);
   A.npairs = K * (K + 1) / 2;
-  // Schur chunks: ranges of kLmChunk landmarks per pose pair while the chunk waves fit one dispatch
-  // round (C3: 45 pairs x 16 ranges); with many pose pairs (C5: K = 29, 435 pairs) fewer, wider
-  // ranges -- each wave then walks more passes, but the chip runs them in one round instead of ~17
   {
-    const int npairs = std::max(A.npairs, 1);
-    A.nchk = std::max(1, std::min((nL + ba::kLmChunk - 1) / ba::kLmChunk, kChunkWaves / npairs));
-    A.lmchunk = std::max(ba::kLmChunk, ((nL + A.nchk - 1) / A.nchk + 63) / 64 * 64);
-    A.nchk = std::max((nL + A.lmchunk - 1) / A.lmchunk, 1);
-    // wide windows (K > the single-wave solve's, fewer than 8 ranges per pair): a diagonal pose pair walks about
-    // (K - 1) / (obs - 1) times an off-diagonal pair's edge pairs (C5: ~970 vs ~170 per range) and set the chunk
-    // phase alone -- its ranges are cut into kDiagSub sub-chunks (the off-diagonal pairs keep theirs)
-    constexpr int kDiagSub = 8;
-    A.dsub = 1;
-    A.lmsub = A.lmchunk;
-    A.K = K;
-    if (!ba::wave_path(K) && A.nchk < 8 && (size_t)A.nchk * (A.npairs + (kDiagSub - 1) * K) <= b->chunk_slots) {
-      A.dsub = kDiagSub;
-      A.lmsub = ((A.lmchunk + kDiagSub - 1) / kDiagSub + 63) / 64 * 64;
-    }
+    const ba::ChunkPlan cp = ba::chunk_plan(nL, K, b->chunk_slots);
+    A.nchk = cp.nchk;
+    A.lmchunk = cp.lmchunk;
+    A.dsub = cp.dsub;
+    A.lmsub = cp.lmsub;
     ba::set_update_geometry(A);
   }
   A.n_line_edges = n_line_local;

@@ -119,6 +119,50 @@ __host__ __device__ inline ChunkGeo chunk_geo(const Active& A, int c) {
   return q;
 }
 
+// pair_chunk's launch order: the chunk of virtual workgroup vb (false: an idle slot of the grid).  With 8 or more
+// landmark ranges (dsub == 1 then, chunk_plan) the workgroups go round-robin over the 8 XCDs (blockIdx % 8) and
+// every chunk of landmark range lb runs on XCD lb % 8, so each XCD's L2 holds only its ranges' records (~1/8 of
+// them), which its ~k_g pose pairs per landmark re-read and update_errors' workgroups of that range (ue_bpr) find
+// there.  Within an XCD the K diagonal pose pairs' chunks take the lowest workgroup ids, longest first: a diagonal
+// chunk walks ~1.5 times an off-diagonal chunk's edge pairs and forms its edges' pose blocks again from the state
+// (C3: 8.4 against 3.5 us median), and pair_index being a row-major upper triangle would otherwise dispatch the
+// diagonal pairs spread through the launch, (K - 1, K - 1) last of all.  The XCD's idle slots (it has one range
+// fewer than another XCD) come last.  With fewer ranges than XCDs (many pose pairs, wide chunks): plain chunk order,
+// every XCD busy.
+__host__ __device__ inline bool chunk_xcd_order(const Active& A) { return A.nchk >= 8 && A.dsub <= 1; }
+__host__ __device__ inline int chunk_grid(const Active& A) {
+  return chunk_xcd_order(A) ? 8 * ((A.nchk + 7) / 8) * A.npairs : chunk_count(A);
+}
+__host__ __device__ inline bool chunk_at(const Active& A, int vb, int& c, ChunkGeo& q) {
+  if (!chunk_xcd_order(A)) {
+    if (vb >= chunk_count(A)) return false;
+    c = vb;
+  } else {
+    const int xcd = vb & 7, slot = vb >> 3, rpx = (A.nchk - xcd + 7) >> 3;  // rpx: this XCD's ranges
+    int t = slot / rpx, a = 0, j = 0;  // pose row a, pair j of the row (0: the diagonal one)
+    const int lb = (slot - t * rpx) * 8 + xcd;
+    if (t < A.K) {
+      a = t;
+    } else {  // the off-diagonal pairs, in pair order
+      t -= A.K;
+      while (a + 1 < A.K && t >= A.K - 1 - a) t -= A.K - 1 - a++;
+      j = t + 1;
+    }
+    if (a + j >= A.K) return false;
+    c = (a * A.K - a * (a - 1) / 2 + j) * A.nchk + lb;
+  }
+  q = chunk_geo(A, c);
+  return true;
+}
+
+// The chunk geometry of a window of nL landmarks and K optimised poses in a handle of chunk_slots chunks,
+// decided here and nowhere else (run_call; carve sizes the handle's chunk buffers with chunk_slots_for).
+struct ChunkPlan {
+  int nchk, lmchunk, dsub, lmsub;
+};
+ChunkPlan chunk_plan(int nL, int K, size_t chunk_slots);
+size_t chunk_slots_for(int max_landmarks, int max_poses);
+
 struct Mail {            // pinned, host-mapped: the per-trial result the host spins on
   double v[4];           // chi2, scale, maxdiag, fail
   unsigned long long seq;
@@ -179,7 +223,12 @@ constexpr int kProfPc = 16, kProfUe = kProfPc + 4 * 4096, kProfX = kProfUe + 4 *
 // [kProfX + i]: setup_kernel's latest landmark / landmark + pose-diagonal / line / line + pose-diagonal / pair
 // block (atomic max over the blocks)
 
-constexpr int kLmChunk = 256;  // landmarks per Schur chunk (4 per lane; 128 measured: 1440 chunk waves exceed one dispatch round)
+// landmarks per Schur chunk (4 per lane).  Measured against it in the C3 pipeline (profiles/ba_chunk_balance.json):
+// 128 -- 1440 chunk waves exceed one dispatch round; 288 / 320 / 384 with the diagonal pairs' ranges cut in 2 or 3
+// (702 .. 594 waves, every chunk ~2 passes) and 256 with them cut in 2 (864 waves) -- the chunk loop alone ends
+// 1.5 .. 2 us sooner, the pipeline's step does not: the diagonal chunks' cost is met by launching them first
+// (chunk_at), not by cutting them
+constexpr int kLmChunk = 256;
 constexpr int kLineBlk = 8;    // line edges per linearisation workgroup
 
 // errors (+ fused final reduction and mailbox post with sequence number seq)

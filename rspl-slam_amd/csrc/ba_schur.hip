@@ -642,9 +642,7 @@ __device__ __forceinline__ void chunk_loop(const Problem& P, const Lin& L, const
 // same launch reads it).  vb is the chunk's virtual workgroup id (XCD-aware order).  Returns true in
 // the wave that completed a pose pair.
 // The chunk of virtual workgroup vb and its pair-list segment (bank-independent: requested before the
-// LM control is read).  XCD-aware chunk order: workgroups go round-robin over the 8 XCDs (blockIdx % 8),
-// so landmark range lb runs on XCD lb % 8 for every pose pair -- each XCD's L2 then holds only its
-// ranges' records (~1/8 of them), which its ~k_g pose pairs per landmark re-read.
+// LM control is read).  The XCD-aware order of the chunks is chunk_at's (ba_kernels.hpp).
 struct ChunkSeg {
   int c, lb, beg, end;
   int pr, c0, c1;  // its pose pair and that pair's chunks
@@ -653,25 +651,13 @@ struct ChunkSeg {
 };
 __device__ __forceinline__ bool chunk_seg(const Active& A, int nq, int vb, ChunkSeg& cs) {
   const int lane = threadIdx.x & 63;
-  if (A.nchk >= 8) {  // (dsub == 1)
-    const int xcd = vb & 7, slot = vb >> 3, rpx = (A.nchk + 7) >> 3;
-    cs.lb = (slot % rpx) * 8 + xcd;
-    cs.pr = slot / rpx;
-    if (cs.lb >= A.nchk || cs.pr >= A.npairs) return false;
-    cs.c = cs.pr * A.nchk + cs.lb;
-    cs.c0 = cs.pr * A.nchk;
-    cs.c1 = cs.c0 + A.nchk;
-    cs.pts = (cs.lb + 1) * A.lmchunk <= nq;
-  } else {  // fewer ranges than XCDs (many pose pairs, wide chunks): plain order, every XCD busy
-    if (vb >= chunk_count(A)) return false;
-    cs.c = vb;
-    const ChunkGeo cg = chunk_geo(A, cs.c);
-    cs.lb = cg.lb;
-    cs.pr = cg.pr;
-    cs.c0 = cg.c0;
-    cs.c1 = cg.c1;
-    cs.pts = cg.gend <= nq;
-  }
+  ChunkGeo cg;
+  if (!chunk_at(A, vb, cs.c, cg)) return false;
+  cs.lb = cg.lb;
+  cs.pr = cg.pr;
+  cs.c0 = cg.c0;
+  cs.c1 = cg.c1;
+  cs.pts = cg.gend <= nq;
   cs.beg = A.pp_off[cs.c];
   cs.end = A.pp_off[cs.c + 1];
   cs.q0 = cs.beg + lane < cs.end ? A.pp[cs.beg + lane] : make_int4(0, 0, 0, 0);
@@ -861,14 +847,9 @@ __global__ __launch_bounds__(256) void cholesky_kernel(Sys S, int n) {
 bool fast_path(int K) { return 6 * K > 0 && 6 * K <= kCholLdsMax; }
 bool wave_path(int K) { return K > 0 && K <= kWaveSolveMaxK; }
 
-// pair_chunk grid: 8 XCD lanes x (landmark ranges per XCD) x pose pairs (idle slots exit)
-static int pair_chunk_blocks(const Active& A) {
-  return A.nchk >= 8 ? 8 * ((A.nchk + 7) / 8) * A.npairs : chunk_count(A);
-}
-
 void launch_chunks(const Problem& P, const Lin& L, const Active& A, const Sys& S, double lambda, const Lin& Ls,
                    const Sys& Ss, bool wave_fused, hipStream_t s) {
-  const dim3 g(pair_chunk_blocks(A)), b(64);
+  const dim3 g(chunk_grid(A)), b(64);  // (idle slots exit)
   switch (wave_fused ? A.K : 0) {
 #define RSPL_CHUNK_CASE(k) \
   case k: hipLaunchKernelGGL(pair_chunk_kernel<6 * k>, g, b, 0, s, P, L, A, S, lambda, Ls, Ss); break;
