@@ -754,8 +754,9 @@ int rspl_lines_debug_canny(rspl_lines* h, int H, int W, uint8_t* half, uint8_t* 
 /*   optimise the kernel of rspl_frame_optimize                              */
 /*   write-back  pose, track ids, kept matches (:586-608, :472-488)          */
 /* rspl_track_enqueue never waits for the device; rspl_track_fetch waits for */
-/* the one event the enqueue recorded.  Line tracking (MatchLines, :455,     */
-/* :490-501) stays with rspl_lines_match, fed from match_kf.                 */
+/* the one event the enqueue recorded.  Line tracking (MatchLines, :455, the  */
+/* id copy of :490-501) and MapBuilder::AddKeyframe's decision (:616-636) are */
+/* one more launch behind the write-back: rspl_track_enqueue_ext (below).    */
 /* ------------------------------------------------------------------------ */
 typedef struct {
   int max_batch;      /* frames per enqueue; also the number of keyframe slots */
@@ -848,6 +849,105 @@ int rspl_track_debug_stage(rspl_track* h, int frame, rspl_track_debug* out);
  * arrays can be read back with rspl_memcpy_d2h. */
 int rspl_track_keyframe_table(rspl_track* h, int slot, int n0, double** d_points, uint8_t** d_state,
                               int32_t** d_track_id);
+
+/* --- the tracking step's line side and keyframe decision ------------------------------------ */
+/* The rest of MapBuilder::TrackFrame and what follows it for a tracked frame, as ONE more launch
+ * behind the write-back of the chain above:
+ *   line tracking   MatchLines between the keyframe's and the frame's points-on-lines
+ *                   (src/map_builder.cc:450-455), fed with the matches BEFORE the removal of
+ *                   :472-488 -- the pairs (match_kf[i], i) -- and the keyframe slot's n0 / the
+ *                   frame's n1 as point counts; then the copy of the keyframe's line track ids and
+ *                   map lines to the matched lines (:490-501).  Line j of the frame receives the id
+ *                   and the map line of keyframe line i iff line_matches[i] == j and that id is
+ *                   >= 0: id 0 IS propagated (unlike the points' `> 0`), the map line is copied
+ *                   even when it is -1, everything else is -1.
+ *   the decision    MapBuilder::AddKeyframe (:616-636) and _last_frame_track_well (:240) on the pose
+ *                   and n_inliers rspl_track_result reports (the last pose when !pose_set, :217).
+ *                   delta_angle = Eigen::AngleAxisd(R_kf^T R).angle(): rotation matrix ->
+ *                   quaternion, 2 atan2(|vec|, |w|), in [0, pi].  The `ref_keyframe ==
+ *                   _last_keyframe` test and the track_last_frame fallback (:218-236, :250) stay
+ *                   with the caller.
+ * The keyframe's AssignPointsToLines runs once per keyframe (rspl_track_set_keyframe_lines), the
+ * frame's inside the added launch.  A point-line assignment that overflows max_pairs, on either
+ * side, leaves every line of the frame unmatched and sets `overflow`; the point results and the
+ * decision are unaffected.  rspl_track_enqueue / rspl_track_fetch are untouched by all of this. */
+typedef struct {
+  int max_lines;  /* lines per frame and per keyframe slot, 1 .. 1024 */
+  int max_pairs;  /* point-line pairs per frame and per slot (the sum of the std::map sizes) */
+} rspl_track_lines_config;
+/* Once per handle, before the first line call: allocates the line buffers.  max_lines outside
+ * [1, 1024], max_pairs <= 0 or a handle with max_keypoints > 4096 is RSPL_E_ARG, checked before
+ * the device is touched. */
+int rspl_track_enable_lines(rspl_track* h, const rspl_track_lines_config* cfg);
+/* The lines of keyframe slot `slot`: DEVICE d_lines [n_lines][4] doubles, the keyframe's DEVICE
+ * SuperPoint records d_features [cap][259] and keypoint count d_n0 (clamped to max_keypoints); HOST
+ * line_track_id [n_lines] (Frame::GetLineTrackId) and line_slot [n_lines] (the id of the map line
+ * held, or -1), copied before the call returns.  Stream-ordered like rspl_track_set_keyframe: one
+ * launch (AssignPointsToLines and the keypoint -> lines incidence, kept in the slot), no host
+ * synchronisation.  n_lines == 0 is valid (the device pointers may then be NULL).  A slot keeps its
+ * lines until they are set again: call this for every new keyframe of the slot. */
+int rspl_track_set_keyframe_lines(rspl_track* h, int slot, int n_lines, const double* d_lines,
+                                  const double* d_features, const int32_t* d_n0, const int32_t* line_track_id,
+                                  const int32_t* line_slot, void* stream);
+
+typedef struct {
+  const double* d_lines;        /* DEVICE [n_lines][4] doubles (rspl_lines_extract_wait_device) */
+  int n_lines;                  /* 0: no line work for this frame */
+  double kf_Twc[16];            /* _last_keyframe->GetPose(), row-major 4x4 */
+  int kf_frame_id, frame_id;
+  int max_num_match;            /* keyframe.max_num_match (configs/configs_euroc.yaml:44: 80) */
+  double max_angle;             /* 0.52 */
+  double max_distance;          /* 0.5 */
+  int max_num_passed_frame;     /* 300 */
+} rspl_track_frame_ext;
+
+/* add_keyframe: the terms of AddKeyframe's return value (:631-634), non-zero = insert a keyframe */
+#define RSPL_TRACK_KF_NOT_ENOUGH_MATCH 1     /* n_inliers < max_num_match */
+#define RSPL_TRACK_KF_LARGE_DELTA_ANGLE 2    /* delta_angle > max_angle */
+#define RSPL_TRACK_KF_LARGE_DISTANCE 4       /* delta_distance > max_distance */
+#define RSPL_TRACK_KF_ENOUGH_PASSED_FRAME 8  /* frame_id - kf_frame_id > max_num_passed_frame */
+
+typedef struct {
+  int n_lines;
+  int n_line_matches;           /* lines with a keyframe line */
+  int n_line_tracks;            /* of those, the lines whose keyframe line carried a track id >= 0 */
+  int overflow;                 /* 1: an assignment exceeded max_pairs, every line is unmatched */
+  int tracked_well;             /* n_inliers >= min_num_match (:240) */
+  int add_keyframe;             /* RSPL_TRACK_KF_* bits */
+  double delta_angle, delta_distance;
+  int passed_frames;
+  /* per line of the frame, caller arrays of max_lines entries (each may be NULL); the first n_lines
+   * are written */
+  int32_t* line_match_kf;       /* the keyframe line, or -1 */
+  int32_t* line_track_id;       /* SetLineTrackId (:498), or -1 */
+  int32_t* line_slot;           /* InsertMapline (:499): the keyframe line's map line, or -1 */
+} rspl_track_ext_result;
+
+/* rspl_track_enqueue plus the launch above: the same chain with the same results, then the line
+ * and decision kernel.  ext[b] goes with frames[b].  Checked before the first launch, besides what
+ * rspl_track_enqueue checks: lines enabled, n_lines in [0, max_lines], d_lines != NULL when
+ * n_lines > 0.  No host synchronisation and no host work between the launches. */
+int rspl_track_enqueue_ext(rspl_track* h, int batch, const rspl_track_frame* frames, const rspl_track_frame_ext* ext,
+                           void* stream);
+/* rspl_track_fetch for an rspl_track_enqueue_ext: the same single wait; ext_results[b] receives
+ * frame b's line results and decision. */
+int rspl_track_fetch_ext(rspl_track* h, rspl_track_result* results, rspl_track_ext_result* ext_results);
+/* debug (parity tests): the point-line assignments behind frame `frame` of the last (fetched)
+ * rspl_track_enqueue_ext, read back as CSR -- line i's keypoints are point_idx[offsets[i] ..
+ * offsets[i + 1]) ascending, dist[] the std::map values -- for the frame and for its keyframe slot.
+ * offsets: max_lines + 1 entries, point_idx / dist: max_pairs entries; every pointer may be NULL.
+ * After an overflow only the offsets are defined. */
+typedef struct {
+  int n_lines, kf_n_lines;
+  int32_t *offsets, *point_idx;
+  double* dist;
+  int32_t *kf_offsets, *kf_point_idx;
+  double* kf_dist;
+} rspl_track_debug_lines_out;
+int rspl_track_debug_lines(rspl_track* h, int frame, rspl_track_debug_lines_out* out);
+/* The DEVICE arrays [max_lines] that receive line_track_id / line_slot of frame `frame` (< max_batch)
+ * of every rspl_track_enqueue_ext, for a consumer on the device ordered behind the enqueue's stream. */
+int rspl_track_frame_lines(rspl_track* h, int frame, int32_t** d_line_track_id, int32_t** d_line_slot);
 
 /* ------------------------------------------------------------------------ */
 /* Keyframe insertion, device side: what turns a tracked stereo frame into a */

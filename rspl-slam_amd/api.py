@@ -639,6 +639,8 @@ _default_pnp_cap = (0,)
 # The tracking step: MapBuilder::TrackFrame + FramePoseOptimization (src/map_builder.cc:448-611)
 # ---------------------------------------------------------------------------
 TRACK_NO_MAPPOINT, TRACK_GOOD, TRACK_NOT_GOOD = 0, 1, 2  # RSPL_TRACK_*: the keyframe table's states
+# RSPL_TRACK_KF_*: the terms of MapBuilder::AddKeyframe in a fetched ``add_keyframe``
+TRACK_KF_NOT_ENOUGH_MATCH, TRACK_KF_LARGE_DELTA_ANGLE, TRACK_KF_LARGE_DISTANCE, TRACK_KF_ENOUGH_PASSED_FRAME = 1, 2, 4, 8
 
 
 class Tracker:
@@ -655,6 +657,7 @@ class Tracker:
         cfg = capi.TrackConfig(self.max_batch, self.max_keypoints, device)
         capi.check(self._lib.rspl_track_create(C.byref(cfg), C.byref(self._h)), "rspl_track_create")
         self._batch = 0
+        self._ext = False  # the last enqueue took the line / decision path
 
     def set_keyframe(self, slot, points, state, track_id, stream=None):
         """The keyframe's table: per keypoint its map point's world position [n0, 3], state [n0]
@@ -672,7 +675,13 @@ class Tracker:
         """frames: list of dicts with the device addresses ``d_features``, ``d_n1``, ``d_idx0``, ``d_idx1``
         (ints or capi.DeviceBuffer), optional ``d_u_right``, ``slot`` (default 0), ``cam`` = (fx, fy, cx, cy,
         bf), ``last_Twc`` [4, 4], and optional ``th_mono_point`` / ``th_stereo_point`` (5.991 / 7.815) and
-        ``min_num_match`` (10)."""
+        ``min_num_match`` (10).
+
+        When any frame carries ``d_lines`` or ``keyframe`` the batch goes through rspl_track_enqueue_ext (after
+        ``enable_lines``): line tracking against the slot's ``set_keyframe_lines`` and the keyframe decision.
+        ``d_lines`` (device [n_lines, 4] doubles) comes with ``n_lines``; ``keyframe`` = dict(Twc [4, 4],
+        frame_id) is the last keyframe, ``frame_id`` this frame's; optional ``max_num_match`` (80),
+        ``max_angle`` (0.52), ``max_distance`` (0.5), ``max_num_passed_frame`` (300)."""
         F = (capi.TrackFrameDesc * max(len(frames), 1))()
         for f, d in zip(F, frames):
             f.slot = d.get("slot", 0)
@@ -684,13 +693,34 @@ class Tracker:
             f.th_mono_point = d.get("th_mono_point", 5.991)
             f.th_stereo_point = d.get("th_stereo_point", 7.815)
             f.min_num_match = d.get("min_num_match", 10)
-        capi.check(self._lib.rspl_track_enqueue(self._h, len(frames), F, _stream_handle(stream)), "rspl_track_enqueue")
+        self._ext = any("d_lines" in d or "keyframe" in d for d in frames)
+        if not self._ext:
+            capi.check(self._lib.rspl_track_enqueue(self._h, len(frames), F, _stream_handle(stream)),
+                       "rspl_track_enqueue")
+        else:
+            X = (capi.TrackFrameExt * max(len(frames), 1))()
+            for x, d in zip(X, frames):
+                v = d.get("d_lines")
+                x.d_lines = v.ptr if isinstance(v, capi.DeviceBuffer) else v
+                x.n_lines = int(d.get("n_lines", 0))
+                kf = d.get("keyframe", {})
+                x.kf_Twc[:] = list(np.asarray(kf.get("Twc", np.eye(4)), np.float64).reshape(16))
+                x.kf_frame_id, x.frame_id = int(kf.get("frame_id", 0)), int(d.get("frame_id", 0))
+                x.max_num_match = int(d.get("max_num_match", 80))
+                x.max_angle = float(d.get("max_angle", 0.52))
+                x.max_distance = float(d.get("max_distance", 0.5))
+                x.max_num_passed_frame = int(d.get("max_num_passed_frame", 300))
+            capi.check(self._lib.rspl_track_enqueue_ext(self._h, len(frames), F, X, _stream_handle(stream)),
+                       "rspl_track_enqueue_ext")
         self._batch = len(frames)
 
     def fetch(self):
         """Wait for the last enqueue.  Returns one dict per frame: pose_q (x, y, z, w), pose_p, pose_set,
         n_inliers, n_pnp_inliers, pnp_used, n_keypoints, n_matches, n_kept, n_mono, n_stereo, rounds,
-        iterations, chi2 and, per current keypoint, match_kf, track_id, kept."""
+        iterations, chi2 and, per current keypoint, match_kf, track_id, kept.  After an enqueue whose
+        frames carried ``d_lines`` or ``keyframe``, also n_lines, n_line_matches, n_line_tracks, overflow,
+        tracked_well, add_keyframe (TRACK_KF_* bits), delta_angle, delta_distance, passed_frames and, per
+        line of the frame, line_match_kf, line_track_id, line_slot."""
         if self._batch == 0:
             return []
         K = self.max_keypoints
@@ -700,7 +730,17 @@ class Tracker:
             a = (np.full(K, -1, np.int32), np.full(K, -1, np.int32), np.zeros(K, np.uint8))
             r.match_kf, r.track_id, r.kept = a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data
             arrs.append(a)
-        capi.check(self._lib.rspl_track_fetch(self._h, R), "rspl_track_fetch")
+        if not self._ext:
+            capi.check(self._lib.rspl_track_fetch(self._h, R), "rspl_track_fetch")
+        else:
+            ML = self.max_lines
+            X = (capi.TrackExtResult * self._batch)()
+            larrs = []
+            for x in X:
+                la = tuple(np.full(ML, -1, np.int32) for _ in range(3))
+                x.line_match_kf, x.line_track_id, x.line_slot = (v.ctypes.data for v in la)
+                larrs.append(la)
+            capi.check(self._lib.rspl_track_fetch_ext(self._h, R, X), "rspl_track_fetch_ext")
         out = []
         for r, a in zip(R, arrs):
             n = r.n_keypoints
@@ -710,7 +750,58 @@ class Tracker:
                             n_stereo=r.n_stereo, rounds=r.rounds, iterations=tuple(r.iterations[:]),
                             chi2=tuple(r.chi2[:]), match_kf=a[0][:n].copy(), track_id=a[1][:n].copy(),
                             kept=a[2][:n].astype(bool)))
+        if self._ext:
+            for o, x, la in zip(out, X, larrs):
+                n = x.n_lines
+                o.update(n_lines=n, n_line_matches=x.n_line_matches, n_line_tracks=x.n_line_tracks,
+                         overflow=bool(x.overflow), tracked_well=bool(x.tracked_well), add_keyframe=x.add_keyframe,
+                         delta_angle=x.delta_angle, delta_distance=x.delta_distance, passed_frames=x.passed_frames,
+                         line_match_kf=la[0][:n].copy(), line_track_id=la[1][:n].copy(), line_slot=la[2][:n].copy())
         return out
+
+    def enable_lines(self, max_lines=512, max_pairs=65536):
+        """Allocate the line side (rspl_track_enable_lines), once per Tracker: up to ``max_lines`` lines per
+        frame and per keyframe slot, ``max_pairs`` point-line pairs per frame and per slot."""
+        cfg = capi.TrackLinesConfig(int(max_lines), int(max_pairs))
+        capi.check(self._lib.rspl_track_enable_lines(self._h, C.byref(cfg)), "rspl_track_enable_lines")
+        self.max_lines, self.max_pairs = int(max_lines), int(max_pairs)
+
+    def set_keyframe_lines(self, slot, n_lines, d_lines, d_features, d_n0, line_track_id, line_slot, stream=None):
+        """The lines of keyframe slot ``slot``: device lines [n_lines, 4], the keyframe's device SuperPoint
+        records and keypoint count (ints or capi.DeviceBuffer), host line track ids and map-line ids [n_lines]."""
+        tid = np.ascontiguousarray(line_track_id, np.int32).reshape(-1)
+        sl = np.ascontiguousarray(line_slot, np.int32).reshape(-1)
+        if not (len(tid) == len(sl) == n_lines):
+            raise ValueError("set_keyframe_lines: line_track_id and line_slot must have n_lines entries")
+        ptr = [v.ptr if isinstance(v, capi.DeviceBuffer) else v for v in (d_lines, d_features, d_n0)]
+        capi.check(self._lib.rspl_track_set_keyframe_lines(self._h, slot, n_lines, *ptr, tid.ctypes.data,
+                                                           sl.ctypes.data, _stream_handle(stream)),
+                   "rspl_track_set_keyframe_lines")
+
+    def frame_lines(self, frame=0):
+        """The device arrays [max_lines] that receive frame ``frame``'s line_track_id / line_slot, for a
+        consumer on the device."""
+        t, s = C.c_void_p(), C.c_void_p()
+        capi.check(self._lib.rspl_track_frame_lines(self._h, frame, C.byref(t), C.byref(s)), "rspl_track_frame_lines")
+        return dict(line_track_id=t.value, line_slot=s.value, capacity=self.max_lines)
+
+    def debug_lines(self, frame=0):
+        """The point-line assignments behind frame ``frame`` of the last (fetched) enqueue with lines, as CSR
+        triples (offsets, point_idx, dist): ``frame`` for the frame's lines, ``keyframe`` for its slot's."""
+        D = capi.TrackDebugLines()
+        ML, cap = self.max_lines, self.max_pairs
+        a = dict(offsets=np.zeros(ML + 1, np.int32), point_idx=np.zeros(cap, np.int32), dist=np.zeros(cap),
+                 kf_offsets=np.zeros(ML + 1, np.int32), kf_point_idx=np.zeros(cap, np.int32), kf_dist=np.zeros(cap))
+        for k, v in a.items():
+            setattr(D, k, v.ctypes.data)
+        capi.check(self._lib.rspl_track_debug_lines(self._h, frame, C.byref(D)), "rspl_track_debug_lines")
+
+        def csr(off, idx, dist, nl):
+            off = off[:nl + 1].copy()
+            n = int(off[-1]) if off[-1] <= cap else 0
+            return off, idx[:n].copy(), dist[:n].copy()
+        return dict(frame=csr(a["offsets"], a["point_idx"], a["dist"], D.n_lines),
+                    keyframe=csr(a["kf_offsets"], a["kf_point_idx"], a["kf_dist"], D.kf_n_lines))
 
     def debug_stage(self, frame=0):
         """The stages of frame ``frame`` of the last (fetched) enqueue, for the parity tests: the compacted

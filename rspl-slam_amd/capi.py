@@ -50,6 +50,8 @@ EXPORTS = [
     "rspl_lines_debug_canny",
     "rspl_track_create", "rspl_track_destroy", "rspl_track_set_keyframe", "rspl_track_enqueue", "rspl_track_fetch",
     "rspl_track_debug_stage", "rspl_track_keyframe_table",
+    "rspl_track_enable_lines", "rspl_track_set_keyframe_lines", "rspl_track_enqueue_ext", "rspl_track_fetch_ext",
+    "rspl_track_debug_lines", "rspl_track_frame_lines",
     "rspl_kf_create", "rspl_kf_destroy", "rspl_kf_enqueue", "rspl_kf_fetch", "rspl_kf_triangulate",
     "rspl_map_insert_keyframe", "rspl_map_get_mapline_observers",
     "rspl_rect_build_maps", "rspl_rect_debug_fixed", "rspl_rect_debug_sizeof", "rspl_rect_debug_copy", "rspl_rect_create", "rspl_rect_destroy",
@@ -135,6 +137,29 @@ class TrackDebug(C.Structure):
                 ("pnp_n_inliers", C.c_int), ("pnp_hypotheses", C.c_int), ("pnp_inlier", C.c_void_p),
                 ("seed_q", C.c_double * 4), ("seed_p", C.c_double * 3), ("pnp_used", C.c_int),
                 ("edge_inlier", C.c_void_p)]
+
+
+class TrackLinesConfig(C.Structure):
+    _fields_ = [("max_lines", C.c_int), ("max_pairs", C.c_int)]
+
+
+class TrackFrameExt(C.Structure):
+    _fields_ = [("d_lines", C.c_void_p), ("n_lines", C.c_int), ("kf_Twc", C.c_double * 16),
+                ("kf_frame_id", C.c_int), ("frame_id", C.c_int), ("max_num_match", C.c_int),
+                ("max_angle", C.c_double), ("max_distance", C.c_double), ("max_num_passed_frame", C.c_int)]
+
+
+class TrackExtResult(C.Structure):
+    _fields_ = [("n_lines", C.c_int), ("n_line_matches", C.c_int), ("n_line_tracks", C.c_int), ("overflow", C.c_int),
+                ("tracked_well", C.c_int), ("add_keyframe", C.c_int), ("delta_angle", C.c_double),
+                ("delta_distance", C.c_double), ("passed_frames", C.c_int), ("line_match_kf", C.c_void_p),
+                ("line_track_id", C.c_void_p), ("line_slot", C.c_void_p)]
+
+
+class TrackDebugLines(C.Structure):
+    _fields_ = [("n_lines", C.c_int), ("kf_n_lines", C.c_int), ("offsets", C.c_void_p), ("point_idx", C.c_void_p),
+                ("dist", C.c_void_p), ("kf_offsets", C.c_void_p), ("kf_point_idx", C.c_void_p),
+                ("kf_dist", C.c_void_p)]
 
 
 class KfConfig(C.Structure):
@@ -286,6 +311,13 @@ def load(path: pathlib.Path = LIB_PATH):
         lib.rspl_track_enqueue.argtypes = [vp, ip, vp, vp]
         lib.rspl_track_fetch.argtypes = [vp, vp]
         lib.rspl_track_debug_stage.argtypes = [vp, ip, C.POINTER(TrackDebug)]
+    if hasattr(lib, "rspl_track_enable_lines"):  # (absent from older builds used as A/B baselines)
+        lib.rspl_track_enable_lines.argtypes = [vp, C.POINTER(TrackLinesConfig)]
+        lib.rspl_track_set_keyframe_lines.argtypes = [vp, ip, ip, vp, vp, vp, vp, vp, vp]
+        lib.rspl_track_enqueue_ext.argtypes = [vp, ip, vp, vp, vp]
+        lib.rspl_track_fetch_ext.argtypes = [vp, vp, vp]
+        lib.rspl_track_debug_lines.argtypes = [vp, ip, C.POINTER(TrackDebugLines)]
+        lib.rspl_track_frame_lines.argtypes = [vp, ip, C.POINTER(vp), C.POINTER(vp)]
     if hasattr(lib, "rspl_kf_create"):
         lib.rspl_track_keyframe_table.argtypes = [vp, ip, ip, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         lib.rspl_kf_create.argtypes = [C.POINTER(KfConfig), C.POINTER(vp)]

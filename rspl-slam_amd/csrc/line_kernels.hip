@@ -10,145 +10,22 @@
 // with contraction off so every product is rounded as the reference's non-FMA x86 build rounds it.
 #include <hip/hip_runtime.h>
 
+#include "line_device.hpp"
 #include "line_kernels.hpp"
 
 namespace rspl {
 namespace lines {
 
-namespace {
-
-// wave-wide exclusive prefix of a per-lane count
-__device__ __forceinline__ int wave_excl(int v, int lane) {
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  return x - v;
-}
-
-// exclusive scan of data[0..n) in LDS by a 1024-thread workgroup (n <= 4 * 1024 per pass, then
-// carried); returns the total.  `part` is 16 ints of LDS.
-__device__ int block_excl_scan(int* data, int n, int* part) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int carry = 0;
-  for (int base = 0; base < n; base += 4096) {
-    int v[4], s = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int i = base + 4 * tid + q;
-      v[q] = i < n ? data[i] : 0;
-      s += v[q];
-    }
-    const int ex = wave_excl(s, lane);
-    if (lane == 63) part[wv] = ex + s;
-    __syncthreads();
-    int wbase = carry;
-    for (int w = 0; w < wv; w++) wbase += part[w];
-    int run = wbase + ex;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int i = base + 4 * tid + q;
-      if (i < n) data[i] = run;
-      run += v[q];
-    }
-    int tot = 0;
-    for (int w = 0; w < 16; w++) tot += part[w];
-    __syncthreads();
-    carry += tot;
-  }
-  return carry;
-}
-
-struct LineEq {
-  double x1, y1, x2, y2, A, B, C, D, lox, hix, loy, hiy;
-};
-
-__device__ __forceinline__ LineEq line_eq(const double* l) {
-#pragma clang fp contract(off)
-  LineEq q;
-  q.x1 = l[0];
-  q.y1 = l[1];
-  q.x2 = l[2];
-  q.y2 = l[3];
-  q.A = q.y2 - q.y1;
-  q.B = q.x1 - q.x2;
-  q.C = q.x2 * q.y1 - q.x1 * q.y2;
-  q.D = sqrt(q.A * q.A + q.B * q.B);
-  q.lox = q.x1 > q.x2 ? q.x2 : q.x1;
-  q.hix = q.x1 > q.x2 ? q.x1 : q.x2;
-  q.loy = q.y1 > q.y2 ? q.y2 : q.y1;
-  q.hiy = q.y1 > q.y2 ? q.y1 : q.y2;
-  return q;
-}
-
-// line_processor.cc:201-212: inside the 3-px-padded box, <= 6 px from the infinite line, and
-// within 3 px of an endpoint or projecting between the endpoints
-__device__ __forceinline__ bool on_line(const LineEq& q, double px, double py, float& d) {
-#pragma clang fp contract(off)
-  if (px < q.lox - 3 || px > q.hix + 3 || py < q.loy - 3 || py > q.hiy + 3) return false;
-  d = (float)(fabs(q.A * px + q.B * py + q.C) / q.D);
-  if (d > 6) return false;
-  const double s1 = (q.x1 - px) * (q.x1 - px) + (q.y1 - py) * (q.y1 - py);
-  const double s2 = (q.x2 - px) * (q.x2 - px) + (q.y2 - py) * (q.y2 - py);
-  const double ls = q.D * q.D;
-  return s1 <= 9 || s2 <= 9 || ((s1 < ls + s2) && (s2 < ls + s1));
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(1024) void assign_kernel(AssignArgs a) {
   extern __shared__ int cnt[];  // [max_lines + 1]
   __shared__ int part[16];
-  __shared__ int total;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int b = blockIdx.x;
   const int nl = min(a.n_lines[b], a.max_lines), np = a.n_points[b];
-  const double* L = a.lines + (size_t)b * a.max_lines * 4;
-  const double* pts = a.pts + (size_t)b * a.pt_batch + a.pt_xoff;
-  int* offs = a.offsets + (size_t)b * (a.max_lines + 1);
-  // pass 1: pairs per line (a wave per line, 64 keypoints per step)
-  for (int l = wv; l < nl; l += 16) {
-    const LineEq q = line_eq(L + 4 * l);
-    int c = 0;
-    for (int j0 = 0; j0 < np; j0 += 64) {
-      const int j = j0 + lane;
-      float d;
-      const bool in = j < np && on_line(q, pts[(size_t)j * a.pt_stride], pts[(size_t)j * a.pt_stride + 1], d);
-      c += __popcll(__ballot(in));
-    }
-    if (lane == 0) cnt[l] = c;
-  }
-  __syncthreads();
-  const int tot = block_excl_scan(cnt, nl, part);
-  if (tid == 0) total = tot;
-  __syncthreads();
-  for (int l = tid; l < nl; l += 1024) offs[l] = cnt[l];
-  if (tid == 0) {
-    offs[nl] = tot;
-    a.status[b] = tot > a.cap ? 1 : 0;
-  }
-  if (total > a.cap) return;  // uniform
-  // pass 2: the same tests, written compacted in keypoint order
-  int* idx = a.idx + (size_t)b * a.cap;
-  double* dist = a.dist + (size_t)b * a.cap;
-  const unsigned long long below = (1ull << lane) - 1;
-  for (int l = wv; l < nl; l += 16) {
-    const LineEq q = line_eq(L + 4 * l);
-    int base = cnt[l];
-    for (int j0 = 0; j0 < np; j0 += 64) {
-      const int j = j0 + lane;
-      float d = 0.f;
-      const bool in = j < np && on_line(q, pts[(size_t)j * a.pt_stride], pts[(size_t)j * a.pt_stride + 1], d);
-      const unsigned long long m = __ballot(in);
-      if (in) {
-        const int pos = base + __popcll(m & below);
-        idx[pos] = j;
-        dist[pos] = (double)d;
-      }
-      base += __popcll(m);
-    }
-  }
+  const int tot = assign_lines(a.lines + (size_t)b * a.max_lines * 4, nl,
+                               a.pts + (size_t)b * a.pt_batch + a.pt_xoff, a.pt_stride, np,
+                               a.offsets + (size_t)b * (a.max_lines + 1), a.idx + (size_t)b * a.cap,
+                               a.dist + (size_t)b * a.cap, a.cap, cnt, part);
+  if (threadIdx.x == 0) a.status[b] = tot > a.cap ? 1 : 0;
 }
 
 // MatchLines.  Phases (workgroup barriers between them):
@@ -226,14 +103,7 @@ __global__ __launch_bounds__(1024) void match_kernel(MatchArgs a) {
         bi = j;
       }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const int ov = __shfl_xor(best, o), oi = __shfl_xor(bi, o);
-      if (ov > best || (ov == best && oi < bi)) {
-        best = ov;
-        bi = oi;
-      }
-    }
+    wave_first_max(best, bi);
     if (lane == 0) rowloc[r] = bi;
   }
   __syncthreads();
@@ -246,14 +116,7 @@ __global__ __launch_bounds__(1024) void match_kernel(MatchArgs a) {
         bi = r;
       }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const int ov = __shfl_xor(best, o), oi = __shfl_xor(bi, o);
-      if (ov > best || (ov == best && oi < bi)) {
-        best = ov;
-        bi = oi;
-      }
-    }
+    wave_first_max(best, bi);
     if (lane == 0) {
       if (best < 2 || rowloc[bi] != j) continue;
       const int sz0 = off0[bi + 1] - off0[bi], sz1 = off1[j + 1] - off1[j];

@@ -3,13 +3,18 @@
 // for a batch of independent frames as one stream-ordered chain: gather | PnP (two kernels) | seed |
 // FrameOptimization | write-back, six launches and one event, no host work in between.  The solvers run
 // on this handle's own Args and buffers (pnp::solve / frame::optimize), all allocated at create.
+// rspl_track_enqueue_ext appends one launch (track_line_kernels.hip): the frame's line tracking against its
+// keyframe slot (:450-455, :490-501) and MapBuilder::AddKeyframe's decision (:616-636); its buffers are
+// allocated by rspl_track_enable_lines.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "common.hpp"
+#include "line_kernels.hpp"
 #include "track_kernels.hpp"
+#include "track_line_kernels.hpp"
 
 using namespace rspl;
 
@@ -36,6 +41,19 @@ struct rspl_track {
   uint8_t* o_kept = nullptr;
   bool pending = false;
   int batch = 0;  // frames of the last enqueue
+  // the line side (rspl_track_enable_lines): its own arena, the slots' id staging, host-mapped parameters / results
+  bool lines_on = false;
+  bool ext = false;  // the last enqueue was rspl_track_enqueue_ext
+  rspl_track_lines_config lcfg{};
+  Arena larena;
+  track::LineArgs la{};
+  std::vector<int> kf_nl;  // lines of each slot, 0 until set
+  char* kfl_stage = nullptr;
+  size_t kfl_stage_slot = 0;
+  std::vector<hipEvent_t> kfl_ev;
+  track::LineParam* lparams = nullptr;
+  track::LineOut* lout = nullptr;
+  int32_t *o_lmatch = nullptr, *o_ltid = nullptr, *o_lslot = nullptr;
 };
 
 namespace {
@@ -86,6 +104,24 @@ int mapped(T** host, T** dev, size_t count) {
       hipHostGetDevicePointer((void**)dev, *host, 0) != hipSuccess)
     return RSPL_E_DEVICE;
   return RSPL_OK;
+}
+
+// what rspl_track_enable_lines allocated (all of it or, after a failure there, a part)
+void release_lines(rspl_track* h) {
+  for (hipEvent_t e : h->kfl_ev)
+    if (e) (void)hipEventDestroy(e);
+  h->kfl_ev.clear();
+  h->larena.release();
+  auto drop = [](auto*& p) {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+  };
+  drop(h->kfl_stage);
+  drop(h->lparams);
+  drop(h->lout);
+  drop(h->o_lmatch);
+  drop(h->o_ltid);
+  drop(h->o_lslot);
 }
 
 }  // namespace
@@ -203,8 +239,11 @@ extern "C" void rspl_track_destroy(rspl_track* h) {
       (void)hipEventSynchronize(e);
       (void)hipEventDestroy(e);
     }
+  for (hipEvent_t e : h->kfl_ev)
+    if (e) (void)hipEventSynchronize(e);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   h->arena.release();
+  release_lines(h);
   if (h->kf_stage) (void)hipHostFree(h->kf_stage);
   if (h->params) (void)hipHostFree(h->params);
   if (h->out) (void)hipHostFree(h->out);
@@ -259,7 +298,9 @@ extern "C" int rspl_track_keyframe_table(rspl_track* h, int slot, int n0, double
   return RSPL_OK;
 }
 
-extern "C" int rspl_track_enqueue(rspl_track* h, int batch, const rspl_track_frame* frames, void* stream) {
+// rspl_track_enqueue (ext == NULL) and rspl_track_enqueue_ext: the same chain, then the line / decision launch
+static int enqueue(rspl_track* h, int batch, const rspl_track_frame* frames, const rspl_track_frame_ext* ext,
+                   void* stream) {
   RSPL_CHECK_ARG(h && (batch == 0 || frames), "rspl_track_enqueue: NULL argument");
   RSPL_CHECK_ARG(batch >= 0 && batch <= h->cfg.max_batch, "batch %d exceeds max_batch %d", batch, h->cfg.max_batch);
   RSPL_CHECK_ARG(!h->pending, "rspl_track_enqueue: the previous enqueue has not been fetched");
@@ -278,8 +319,36 @@ extern "C" int rspl_track_enqueue(rspl_track* h, int batch, const rspl_track_fra
     RSPL_CHECK_ARG(finite && fr.fx != 0 && fr.fy != 0, "frame %d: bad camera or last pose", b);
     // the edge count is the device's; its bound min(n0, max_keypoints) = n0 sizes the launch
     max_n = std::max(max_n, h->n0[fr.slot]);
+    if (ext) {
+      const rspl_track_frame_ext& x = ext[b];
+      RSPL_CHECK_ARG(x.n_lines >= 0 && x.n_lines <= h->lcfg.max_lines, "frame %d: n_lines %d outside [0, %d]", b,
+                     x.n_lines, h->lcfg.max_lines);
+      RSPL_CHECK_ARG(x.n_lines == 0 || x.d_lines, "frame %d: NULL d_lines with n_lines %d", b, x.n_lines);
+      bool fin = std::isfinite(x.max_angle) && std::isfinite(x.max_distance);
+      for (int k = 0; k < 12; k++) fin = fin && std::isfinite(x.kf_Twc[k]);
+      RSPL_CHECK_ARG(fin, "frame %d: bad keyframe pose or thresholds", b);
+    }
   }
   if (batch == 0) return RSPL_OK;
+  for (int b = 0; ext && b < batch; b++) {
+    const rspl_track_frame_ext& x = ext[b];
+    track::LineParam& L = h->lparams[b];
+    L.lines = x.d_lines;
+    L.n_lines = x.n_lines;
+    L.slot = frames[b].slot;
+    L.kf_n_lines = h->kf_nl[L.slot];
+    L.kf_frame_id = x.kf_frame_id;
+    L.frame_id = x.frame_id;
+    L.max_num_match = x.max_num_match;
+    L.max_num_passed_frame = x.max_num_passed_frame;
+    L.pad = 0;
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) L.kf_R[3 * r + c] = x.kf_Twc[4 * r + c];
+      L.kf_t[r] = x.kf_Twc[4 * r + 3];
+    }
+    L.max_angle = x.max_angle;
+    L.max_distance = x.max_distance;
+  }
   for (int b = 0; b < batch; b++) {
     const rspl_track_frame& fr = frames[b];
     track::Param& P = h->params[b];
@@ -314,15 +383,162 @@ extern "C" int rspl_track_enqueue(rspl_track* h, int batch, const rspl_track_fra
   RSPL_HIP(track::seed(h->ta, batch, st));
   RSPL_HIP(frame::optimize(h->fa, batch, max_n, st));
   RSPL_HIP(track::write_back(h->ta, batch, st));
+  if (ext) RSPL_HIP(track::frame_lines(h->ta, h->la, batch, st));
   RSPL_HIP(hipEventRecord(h->done, st));
   h->pending = true;
   h->batch = batch;
+  h->ext = ext != nullptr;
   return RSPL_OK;
 }
 
-extern "C" int rspl_track_fetch(rspl_track* h, rspl_track_result* res) {
+extern "C" int rspl_track_enqueue(rspl_track* h, int batch, const rspl_track_frame* frames, void* stream) {
+  return enqueue(h, batch, frames, nullptr, stream);
+}
+
+extern "C" int rspl_track_enqueue_ext(rspl_track* h, int batch, const rspl_track_frame* frames,
+                                      const rspl_track_frame_ext* ext, void* stream) {
+  RSPL_CHECK_ARG(h && (batch == 0 || ext), "rspl_track_enqueue_ext: NULL argument");
+  RSPL_CHECK_ARG(h->lines_on, "rspl_track_enqueue_ext: call rspl_track_enable_lines first");
+  if (batch == 0) ext = nullptr;  // nothing is launched, as rspl_track_enqueue
+  return enqueue(h, batch, frames, ext, stream);
+}
+
+extern "C" int rspl_track_enable_lines(rspl_track* h, const rspl_track_lines_config* cfg) {
+  // (the configuration first, so that it is judged on its own, whatever the handle)
+  RSPL_CHECK_ARG(cfg, "rspl_track_enable_lines: NULL configuration");
+  RSPL_CHECK_ARG(cfg->max_lines >= 1 && cfg->max_lines <= 1024, "rspl_track_enable_lines: max_lines %d outside [1, 1024]",
+                 cfg->max_lines);
+  RSPL_CHECK_ARG(cfg->max_pairs > 0, "rspl_track_enable_lines: max_pairs %d is not positive", cfg->max_pairs);
+  RSPL_CHECK_ARG(h, "rspl_track_enable_lines: NULL handle");
+  RSPL_CHECK_ARG(h->cfg.max_keypoints <= lines::kMaxPointsLds,
+                 "rspl_track_enable_lines: max_keypoints %d exceeds the %d a line workgroup holds", h->cfg.max_keypoints,
+                 lines::kMaxPointsLds);
+  RSPL_CHECK_ARG(!h->lines_on, "rspl_track_enable_lines: already enabled");
+  RSPL_CHECK_ARG(!h->pending, "rspl_track_enable_lines: an enqueue is in flight, fetch it first");
+  RSPL_HIP(hipSetDevice(h->cfg.device));
+  const size_t S = h->cfg.max_batch, K = h->cfg.max_keypoints, ML = cfg->max_lines, cap = cfg->max_pairs;
+  track::LineArgs& g = h->la;
+  auto carve = [&](auto& A) {
+    g.kf_off = A.template take<int>(S * (ML + 1));
+    g.kf_idx = A.template take<int>(S * cap);
+    g.kf_dist = A.template take<double>(S * cap);
+    g.kf_kstart = A.template take<int>(S * (K + 1));
+    g.kf_kline = A.template take<int>(S * cap);
+    g.kf_status = A.template take<int>(S);
+    g.kf_ltid = A.template take<int32_t>(S * ML);
+    g.kf_lslot = A.template take<int32_t>(S * ML);
+    g.off = A.template take<int>(S * (ML + 1));
+    g.idx = A.template take<int>(S * cap);
+    g.dist = A.template take<double>(S * cap);
+    g.kline = A.template take<int>(S * cap);
+    g.M = A.template take<int>(S * ML * ML);
+    g.line_match = A.template take<int32_t>(S * ML);
+    g.line_tid = A.template take<int32_t>(S * ML);
+    g.line_slot = A.template take<int32_t>(S * ML);
+  };
+  Count sz;
+  carve(sz);
+  int rc = h->larena.reserve(sz.used + 256);
+  if (rc) return rc;
+  carve(h->larena);
+  h->kf_nl.assign(S, 0);
+  h->kfl_ev.assign(S, nullptr);
+  h->kfl_stage_slot = (2 * sizeof(int32_t) * ML + 255) & ~size_t(255);
+  bool ok = hipHostMalloc((void**)&h->kfl_stage, h->kfl_stage_slot * S, hipHostMallocDefault) == hipSuccess &&
+            mapped(&h->lparams, const_cast<track::LineParam**>(&g.lparams), S) == RSPL_OK &&
+            mapped(&h->lout, &g.out, S) == RSPL_OK && mapped(&h->o_lmatch, &g.o_line_match, S * ML) == RSPL_OK &&
+            mapped(&h->o_ltid, &g.o_line_tid, S * ML) == RSPL_OK && mapped(&h->o_lslot, &g.o_line_slot, S * ML) == RSPL_OK;
+  for (size_t s = 0; ok && s < S; s++) ok = hipEventCreateWithFlags(&h->kfl_ev[s], hipEventDisableTiming) == hipSuccess;
+  // (zeroed once: a slot whose lines were never set has status 0, and a debug read-back is defined)
+  ok = ok && hipMemset(h->larena.base, 0, h->larena.used) == hipSuccess;
+  if (!ok) {
+    set_error("rspl_track_enable_lines: event / pinned allocation failed");
+    release_lines(h);
+    return RSPL_E_DEVICE;
+  }
+  g.K = (int)K;
+  g.max_lines = (int)ML;
+  g.cap = (int)cap;
+  h->lcfg = *cfg;
+  h->lines_on = true;
+  return RSPL_OK;
+}
+
+extern "C" int rspl_track_set_keyframe_lines(rspl_track* h, int slot, int n_lines, const double* d_lines,
+                                             const double* d_features, const int32_t* d_n0,
+                                             const int32_t* line_track_id, const int32_t* line_slot, void* stream) {
+  RSPL_CHECK_ARG(h, "rspl_track_set_keyframe_lines: NULL handle");
+  RSPL_CHECK_ARG(h->lines_on, "rspl_track_set_keyframe_lines: call rspl_track_enable_lines first");
+  RSPL_CHECK_ARG(slot >= 0 && slot < h->cfg.max_batch, "slot %d outside [0, %d)", slot, h->cfg.max_batch);
+  RSPL_CHECK_ARG(n_lines >= 0 && n_lines <= h->lcfg.max_lines, "n_lines %d outside [0, %d]", n_lines, h->lcfg.max_lines);
+  RSPL_CHECK_ARG(n_lines == 0 || (d_lines && d_features && d_n0 && line_track_id && line_slot),
+                 "rspl_track_set_keyframe_lines: NULL array");
+  RSPL_CHECK_ARG(!h->pending, "rspl_track_set_keyframe_lines: an enqueue is in flight, fetch it first");
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  if (n_lines) {
+    const size_t ML = h->lcfg.max_lines;
+    // the slot's staging may still feed an earlier upload: that copy (only it) is waited for
+    RSPL_HIP(hipEventSynchronize(h->kfl_ev[slot]));
+    int32_t* sg = (int32_t*)(h->kfl_stage + h->kfl_stage_slot * slot);
+    memcpy(sg, line_track_id, sizeof(int32_t) * n_lines);
+    memcpy(sg + ML, line_slot, sizeof(int32_t) * n_lines);
+    RSPL_HIP(hipMemcpyAsync(h->la.kf_ltid + ML * slot, sg, sizeof(int32_t) * n_lines, hipMemcpyHostToDevice, st));
+    RSPL_HIP(hipMemcpyAsync(h->la.kf_lslot + ML * slot, sg + ML, sizeof(int32_t) * n_lines, hipMemcpyHostToDevice, st));
+    RSPL_HIP(hipEventRecord(h->kfl_ev[slot], st));
+    RSPL_HIP(track::kf_lines(h->la, slot, d_lines, n_lines, d_features, d_n0, st));
+  }
+  h->kf_nl[slot] = n_lines;  // (0 lines: nothing of the slot is read)
+  return RSPL_OK;
+}
+
+extern "C" int rspl_track_frame_lines(rspl_track* h, int frame, int32_t** d_line_track_id, int32_t** d_line_slot) {
+  RSPL_CHECK_ARG(h && d_line_track_id && d_line_slot, "rspl_track_frame_lines: NULL argument");
+  RSPL_CHECK_ARG(h->lines_on, "rspl_track_frame_lines: call rspl_track_enable_lines first");
+  RSPL_CHECK_ARG(frame >= 0 && frame < h->cfg.max_batch, "frame %d outside [0, %d)", frame, h->cfg.max_batch);
+  *d_line_track_id = h->la.line_tid + (size_t)h->lcfg.max_lines * frame;
+  *d_line_slot = h->la.line_slot + (size_t)h->lcfg.max_lines * frame;
+  return RSPL_OK;
+}
+
+extern "C" int rspl_track_debug_lines(rspl_track* h, int frame, rspl_track_debug_lines_out* d) {
+  RSPL_CHECK_ARG(h && d, "rspl_track_debug_lines: NULL argument");
+  RSPL_CHECK_ARG(!h->pending && h->ext, "rspl_track_debug_lines: fetch an rspl_track_enqueue_ext first");
+  RSPL_CHECK_ARG(frame >= 0 && frame < h->batch, "frame %d not in the last batch", frame);
+  const track::LineArgs& g = h->la;
+  const track::LineParam& L = h->lparams[frame];
+  const size_t ML = g.max_lines, cap = g.cap;
+  auto get = [](void* dst, const void* src, size_t bytes) {
+    return dst && bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+  };
+  // one side's CSR: the offsets, then as many pairs as they count (none after an overflow)
+  auto side = [&](int nl, const int* off, const int* idx, const double* dist, int32_t* o_off, int32_t* o_idx,
+                  double* o_dist) -> hipError_t {
+    if (nl == 0) {
+      if (o_off) o_off[0] = 0;
+      return hipSuccess;
+    }
+    int tot = 0;
+    hipError_t e = get(o_off, off, sizeof(int) * (nl + 1));
+    if (e == hipSuccess) e = get(&tot, off + nl, sizeof(int));
+    const size_t n = (size_t)tot <= cap ? tot : 0;
+    if (e == hipSuccess) e = get(o_idx, idx, sizeof(int) * n);
+    if (e == hipSuccess) e = get(o_dist, dist, sizeof(double) * n);
+    return e;
+  };
+  d->n_lines = L.n_lines;
+  d->kf_n_lines = L.kf_n_lines;
+  RSPL_HIP(side(L.n_lines, g.off + (ML + 1) * frame, g.idx + cap * frame, g.dist + cap * frame, d->offsets,
+                d->point_idx, d->dist));
+  RSPL_HIP(side(L.kf_n_lines, g.kf_off + (ML + 1) * L.slot, g.kf_idx + cap * L.slot, g.kf_dist + cap * L.slot,
+                d->kf_offsets, d->kf_point_idx, d->kf_dist));
+  return RSPL_OK;
+}
+
+// rspl_track_fetch (xres == NULL) and rspl_track_fetch_ext
+static int fetch(rspl_track* h, rspl_track_result* res, rspl_track_ext_result* xres) {
   RSPL_CHECK_ARG(h && res, "rspl_track_fetch: NULL argument");
   RSPL_CHECK_ARG(h->pending, "rspl_track_fetch: nothing was enqueued");
+  RSPL_CHECK_ARG(!xres || h->ext, "rspl_track_fetch_ext: the enqueue was not rspl_track_enqueue_ext");
   RSPL_HIP(hipEventSynchronize(h->done));
   h->pending = false;
   const size_t K = h->cfg.max_keypoints;
@@ -348,7 +564,31 @@ extern "C" int rspl_track_fetch(rspl_track* h, rspl_track_result* res) {
     if (r.track_id) memcpy(r.track_id, h->o_track_id + K * b, sizeof(int32_t) * n);
     if (r.kept) memcpy(r.kept, h->o_kept + K * b, n);
   }
+  for (int b = 0; xres && b < h->batch; b++) {
+    const track::LineOut& o = h->lout[b];
+    rspl_track_ext_result& x = xres[b];
+    x.n_lines = o.n_lines;
+    x.n_line_matches = o.n_matches;
+    x.n_line_tracks = o.n_tracks;
+    x.overflow = o.overflow;
+    x.tracked_well = o.tracked_well;
+    x.add_keyframe = o.add_keyframe;
+    x.delta_angle = o.delta_angle;
+    x.delta_distance = o.delta_distance;
+    x.passed_frames = o.passed_frames;
+    const size_t ML = h->lcfg.max_lines, n = (size_t)std::min<int>(std::max(o.n_lines, 0), (int)ML);
+    if (x.line_match_kf) memcpy(x.line_match_kf, h->o_lmatch + ML * b, sizeof(int32_t) * n);
+    if (x.line_track_id) memcpy(x.line_track_id, h->o_ltid + ML * b, sizeof(int32_t) * n);
+    if (x.line_slot) memcpy(x.line_slot, h->o_lslot + ML * b, sizeof(int32_t) * n);
+  }
   return RSPL_OK;
+}
+
+extern "C" int rspl_track_fetch(rspl_track* h, rspl_track_result* res) { return fetch(h, res, nullptr); }
+
+extern "C" int rspl_track_fetch_ext(rspl_track* h, rspl_track_result* res, rspl_track_ext_result* xres) {
+  RSPL_CHECK_ARG(xres, "rspl_track_fetch_ext: NULL argument");
+  return fetch(h, res, xres);
 }
 
 extern "C" int rspl_track_debug_stage(rspl_track* h, int frame, rspl_track_debug* d) {
