@@ -11,6 +11,7 @@
  *                   include/g2o_optimization/g2o_optimization.h:20-22 -> rspl_frame_*
  *   SolvePnPWithCV  include/g2o_optimization/g2o_optimization.h:24    -> rspl_pnp_*
  *   Camera          include/camera.h:15-40          -> rspl_rect_*
+ *   RCF             include/rcf.h:25-57             -> rspl_rcf_*
  * Plain pointers and sizes only; no Eigen / OpenCV / torch types.  Every call
  * returns RSPL_OK (0) or a negative RSPL_E_* code (rspl_last_error() has the
  * text).  Handles are NOT thread-safe: callers serialise, exactly as the
@@ -1161,6 +1162,61 @@ int rspl_rect_enqueue_device(rspl_rect* h, int batch, const uint8_t* d_raw, size
 /* Camera::UndistortImage: host images in (one row stride for both), rectified host images out. */
 int rspl_rect_pair(rspl_rect* h, const uint8_t* left, const uint8_t* right, size_t stride, uint8_t* left_rect,
                    uint8_t* right_rect, size_t out_stride);
+
+/* ------------------------------------------------------------------------ */
+/* RCF edge network: RCF::infer (src/rcf.cpp:95-135), which                  */
+/* MapBuilder::AddInput runs on both rectified images of every frame         */
+/* (src/map_builder.cc:86-121) and whose edge image, not the camera image,   */
+/* the line detector then reads (src/map_builder.cc:286, :327).  The network */
+/* is the VGG16-based RCF of yun-liu/RCF-PyTorch, the weights an RSPLWT01     */
+/* blob with that model's state_dict names (conv1_1 .. conv5_3, their _down   */
+/* 1x1 convs, score_dsn1..5, score_fuse).  The input is the gray u8 image as  */
+/* raw floats 0..255 (src/rcf.cpp:161-192; the three identical input          */
+/* channels are folded into conv1_1's weights).  The reference's engine file  */
+/* and ONNX are not available, so parity with its binding "230" is unpinned:  */
+/* `output` selects which of the network's six maps becomes the edge image.   */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  int max_height, max_width; /* 16..2048 each: every call's H, W lie in 16..max */
+  int max_batch;             /* images per rspl_rcf_infer_device call, 1..64 */
+  int precision;             /* RSPL_PREC_FP32 (the reference: kFP16 is commented out, src/rcf.cpp:51) or
+                              * RSPL_PREC_FP16 */
+  int output;                /* 0..4: sigmoid(so_1..5), 5: sigmoid(fuse) (RCF's result; the default to use) */
+  int device;
+} rspl_rcf_config;
+
+typedef struct rspl_rcf rspl_rcf;
+
+/* sizeof of 0: rspl_rcf_config as the library was built (-1 otherwise) */
+int rspl_rcf_debug_sizeof(int which);
+/* RCF::build (src/rcf.cpp:25-93) without an engine to deserialise: reads the blob, lays the weights out for
+ * the kernels and allocates all device memory.  A bad config is RSPL_E_ARG before the blob or a device is
+ * touched; a missing or mis-shaped tensor is RSPL_E_WEIGHTS and rspl_last_error() names it. */
+int rspl_rcf_create(const rspl_rcf_config* cfg, const char* weights_path, rspl_rcf** out);
+void rspl_rcf_destroy(rspl_rcf* h);
+/* RCF::infer (src/rcf.cpp:95-135) with process_output's conversion (src/rcf.cpp:147-152): gray u8 host image
+ * [H][stride] in, edge image [H][W] u8 out, (uint8)(unsigned)(255.0f - p * 255.0f). */
+int rspl_rcf_infer(rspl_rcf* h, const uint8_t* image, int H, int W, size_t stride, uint8_t* edges);
+/* The same on `batch` device images, image b at d_images + b*pitch with row stride `stride` bytes (the layout
+ * rspl_rect_enqueue_device writes), edge image b to d_edges + b*out_pitch with row stride out_stride.
+ * Stream-ordered, never waits for the device; bytes outside the W pixels of a row are not written.  H or W
+ * outside 16..max, strides below W, pitches below an image and batch > max_batch are RSPL_E_ARG before any
+ * device call.  stream may be NULL (the handle's own). */
+int rspl_rcf_infer_device(rspl_rcf* h, const uint8_t* d_images, int batch, int H, int W, size_t stride, size_t pitch,
+                          uint8_t* d_edges, size_t out_stride, size_t out_pitch, void* stream);
+/* Parity hook: the pre-sigmoid map `which` (0..4: so_1..5 upsampled and cropped, 5: fuse) of image b of the
+ * last call, [H][W] floats to the host.  Waits for that call. */
+int rspl_rcf_debug_logits(rspl_rcf* h, int b, int which, float* out);
+/* Device time per stage, from events on the call's stream (never a host wait): profile(1) starts collecting,
+ * stage_times adds up the RSPL_RCF_STAGES segments of the calls since -- stages 1..5 (each its pool, its 3x3
+ * convs and their side branches) and the tail -- in milliseconds, and the number of calls. */
+#define RSPL_RCF_STAGES 6
+int rspl_rcf_profile(rspl_rcf* h, int enable);
+int rspl_rcf_stage_times(rspl_rcf* h, float* ms, int* calls);
+/* Test hook: the 3x3 convolutions' workgroup tile, 8 or 16 rows (of 16 columns and 64 channels), for the calls
+ * that follow; 0 (the default) chooses per layer from the launch's size, which small test images never carry
+ * past the threshold.  The results do not depend on it, bit for bit. */
+int rspl_rcf_debug_tile_rows(rspl_rcf* h, int rows);
 
 #ifdef __cplusplus
 }

@@ -6,8 +6,9 @@ this package only mirrors the reference's C++ interface over its C ABI.
 """
 import importlib
 
-from . import capi, weights, synthetic, ba_types, hostgroup, mapping, trajectory, sequence, lines, camera  # noqa: F401
+from . import capi, weights, synthetic, ba_types, hostgroup, mapping, trajectory, sequence, lines, camera, rcf  # noqa: F401
 from .camera import Camera, Rectifier  # noqa: F401
+from .rcf import RCF  # noqa: F401
 
 _API = ("SuperPoint", "SuperPointConfig", "SuperGlue", "SuperGlueConfig", "PointMatching",
         "LocalmapOptimization", "LocalBA", "FrameOptimization", "FrameBA",

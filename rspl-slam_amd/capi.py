@@ -56,6 +56,8 @@ EXPORTS = [
     "rspl_map_insert_keyframe", "rspl_map_get_mapline_observers",
     "rspl_rect_build_maps", "rspl_rect_debug_fixed", "rspl_rect_debug_sizeof", "rspl_rect_debug_copy", "rspl_rect_create", "rspl_rect_destroy",
     "rspl_rect_get_maps", "rspl_rect_set_maps", "rspl_rect_enqueue_device", "rspl_rect_pair",
+    "rspl_rcf_debug_sizeof", "rspl_rcf_create", "rspl_rcf_destroy", "rspl_rcf_infer", "rspl_rcf_infer_device",
+    "rspl_rcf_debug_logits", "rspl_rcf_debug_tile_rows", "rspl_rcf_profile", "rspl_rcf_stage_times",
 ]
 
 
@@ -192,6 +194,11 @@ class RectCamera(C.Structure):
 class RectConfig(C.Structure):
     _fields_ = [("height", C.c_int), ("width", C.c_int), ("distortion_type", C.c_int), ("cam", RectCamera * 2),
                 ("max_batch", C.c_int), ("device", C.c_int)]
+
+
+class RcfConfig(C.Structure):
+    _fields_ = [("max_height", C.c_int), ("max_width", C.c_int), ("max_batch", C.c_int), ("precision", C.c_int),
+                ("output", C.c_int), ("device", C.c_int)]
 
 
 class RsplError(RuntimeError):
@@ -339,6 +346,18 @@ def load(path: pathlib.Path = LIB_PATH):
         lib.rspl_rect_set_maps.argtypes = [vp, ip, vp, vp]
         lib.rspl_rect_enqueue_device.argtypes = [vp, ip, vp, sz, sz, C.POINTER(ip), vp, sz, sz, vp]
         lib.rspl_rect_pair.argtypes = [vp, vp, vp, sz, vp, vp, sz]
+    if hasattr(lib, "rspl_rcf_create"):
+        sz = C.c_size_t
+        lib.rspl_rcf_debug_sizeof.argtypes = [ip]
+        lib.rspl_rcf_create.argtypes = [C.POINTER(RcfConfig), C.c_char_p, C.POINTER(vp)]
+        lib.rspl_rcf_destroy.argtypes = [vp]
+        lib.rspl_rcf_destroy.restype = None
+        lib.rspl_rcf_infer.argtypes = [vp, vp, ip, ip, sz, vp]
+        lib.rspl_rcf_infer_device.argtypes = [vp, vp, ip, ip, ip, sz, sz, vp, sz, sz, vp]
+        lib.rspl_rcf_debug_logits.argtypes = [vp, ip, ip, vp]
+        lib.rspl_rcf_debug_tile_rows.argtypes = [vp, ip]
+        lib.rspl_rcf_profile.argtypes = [vp, ip]
+        lib.rspl_rcf_stage_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(ip)]
     _lib = lib
     return lib
 

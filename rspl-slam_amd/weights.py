@@ -116,6 +116,37 @@ def superglue_shapes(n_layers: int = 18) -> "OrderedDict[str, tuple]":
     return d
 
 
+RCF_STAGES = ((2, 64), (2, 128), (3, 256), (3, 512), (3, 512))  # (3x3 convs, channels) per stage
+RCF_SIDE = 21
+
+
+def rcf_shapes() -> "OrderedDict[str, tuple]":
+    """The VGG16-based RCF's state_dict (yun-liu/RCF-PyTorch, the network behind the reference's src/rcf.cpp):
+    conv{s}_{k} (3x3), conv{s}_{k}_down (1x1, C -> 21), score_dsn{s} (1x1, 21 -> 1), score_fuse (1x1, 5 -> 1)."""
+    d = OrderedDict()
+    cin = 3
+    for s, (n, c) in enumerate(RCF_STAGES, 1):
+        for k in range(1, n + 1):
+            d[f"conv{s}_{k}.weight"] = (c, cin, 3, 3)
+            d[f"conv{s}_{k}.bias"] = (c,)
+            cin = c
+    for s, (n, c) in enumerate(RCF_STAGES, 1):
+        for k in range(1, n + 1):
+            d[f"conv{s}_{k}_down.weight"] = (RCF_SIDE, c, 1, 1)
+            d[f"conv{s}_{k}_down.bias"] = (RCF_SIDE,)
+    for s in range(1, len(RCF_STAGES) + 1):
+        d[f"score_dsn{s}.weight"] = (1, RCF_SIDE, 1, 1)
+        d[f"score_dsn{s}.bias"] = (1,)
+    d["score_fuse.weight"] = (1, len(RCF_STAGES), 1, 1)
+    d["score_fuse.bias"] = (1,)
+    return d
+
+
+# The network reads the raw gray values 0..255 (src/rcf.cpp:161-192); with He-uniform weights throughout they
+# saturate the sigmoid almost everywhere.  A gain of 0.01 on the first layer spreads the fused logits over the
+# whole transfer curve (tests/test_rcf_cpu.py asserts >= 128 distinct edge levels per test case).
+RCF_WEIGHT_GAIN = {"conv1_1.weight": 0.01}
+
 # Synthetic-weight profile.  Scales chosen (and measured, see DESIGN.md) so
 # that (a) SuperPoint scores are distinct (reference top-k uses a non-stable
 # std::sort, SURVEY F7) and (b) SuperGlue descriptors keep their identity
@@ -191,6 +222,10 @@ def superglue_synth(seed: int = 2, profile: str = "default") -> "OrderedDict[str
     return synth(superglue_shapes(), seed, SG_PROFILES[profile])
 
 
+def rcf_synth(seed: int = 7) -> "OrderedDict[str, np.ndarray]":
+    return synth(rcf_shapes(), seed, RCF_WEIGHT_GAIN)
+
+
 # --------------------------------------------------------------------------
 # blob I/O
 # --------------------------------------------------------------------------
@@ -245,6 +280,18 @@ def ensure_blobs(directory, sp_seed: int = 1, sg_seed: int = 2):
     if not os.path.exists(sg):
         write_blob(sg, superglue_synth(sg_seed))
     return sp, sg
+
+
+def ensure_rcf_blob(directory, seed: int = 7):
+    """weights/rcf_synth_s{seed}.bin (written if absent; 14.7 M parameters, 59 MB)."""
+    import os
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, f"rcf_synth_s{seed}.bin")
+    if not os.path.exists(path):
+        tmp = f"{path}.{os.getpid()}.tmp"  # (several test processes may get here at once)
+        write_blob(tmp, rcf_synth(seed))
+        os.replace(tmp, path)
+    return path
 
 
 def ensure_sg_profile_blob(directory, profile: str = "c1", sg_seed: int = 2):
