@@ -264,8 +264,12 @@ void rspl_sg_destroy(rspl_sg* sg);
 
 /* ------------------------------------------------------------------------ */
 /* PointMatching (src/point_matching.cc): normalise, SuperGlue, mutual check, */
-/* DMatch(i, j, 1 - (ms0 + ms1)/2).  outlier_rejection (F-matrix RANSAC,     */
-/* default off in the reference) is not implemented: RSPL_E_ARG if set.      */
+/* DMatch(i, j, 1 - (ms0 + ms1)/2).  outlier_rejection (default off in the   */
+/* reference) filters the matches through cv::findFundamentalMat(FM_RANSAC,  */
+/* 3, 0.99) (:34-45) as rspl_fm_solve computes it, on an rspl_fm handle the  */
+/* rspl_sg handle creates on first use (sized by its max_keypoints, freed by */
+/* rspl_sg_destroy); the surviving matches stay in order.  Fewer than 7      */
+/* matches, or no model: nothing is rejected.                                */
 /* ------------------------------------------------------------------------ */
 typedef struct {
   int32_t query_idx;
@@ -1217,6 +1221,88 @@ int rspl_rcf_stage_times(rspl_rcf* h, float* ms, int* calls);
  * that follow; 0 (the default) chooses per layer from the launch's size, which small test images never carry
  * past the threshold.  The results do not depend on it, bit for bit. */
 int rspl_rcf_debug_tile_rows(rspl_rcf* h, int rows);
+
+/* ------------------------------------------------------------------------ */
+/* F-matrix RANSAC: cv::findFundamentalMat(points0, points1, cv::FM_RANSAC,  */
+/* 3, 0.99, inliers) as PointMatching::MatchingPoints calls it               */
+/* (src/point_matching.cc:34-45), for a batch of independent frames.  A      */
+/* restatement of OpenCV 4.2's published algorithm (tests/fm_ref.py states   */
+/* it; OpenCV itself is not available, so parity with it is unpinned):       */
+/* cv::RNG seeded (uint64)-1, subsets of 7 distinct indices, checkSubset,    */
+/* the 7-point solver (up to three models), max(d1^2 s1, d2^2 s2) rounded to */
+/* float against (float)(threshold^2), the sequential acceptance with        */
+/* RANSACUpdateNumIters, no refit.  All iterations are solved side by side   */
+/* on the device and the acceptance replayed afterwards.                     */
+/*   n < 7   no model, nothing rejected: n_inliers = -1, inlier[] all 1      */
+/*   n == 7  the 7-point solver directly, its first model, inlier[] all 1    */
+/*   n >= 8  RANSAC; no model ever accepted: n_inliers = -1, inlier[] all 1  */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  int max_batch;
+  int max_matches; /* matches per frame; on the device-resident path also the keypoints per image considered */
+  int max_iters;   /* 1000 (RANSACPointSetRegistrator's maxIters); at most 1000 */
+  int device;
+} rspl_fm_config;
+
+typedef struct {
+  int n;
+  const double* points0; /* [n][2] pixels */
+  const double* points1;
+  double threshold;      /* 3.0 */
+  double confidence;     /* 0.99 */
+} rspl_fm_problem;
+
+typedef struct {
+  uint8_t* inlier; /* [n], may be NULL */
+  int n_inliers;   /* -1: no model, nothing rejected */
+  int hypotheses;  /* iterations evaluated */
+  double F[9];     /* row-major, x1^T F x0 = 0; zeros without a model */
+} rspl_fm_result;
+
+typedef struct rspl_fm rspl_fm;
+
+int rspl_fm_create(const rspl_fm_config* cfg, rspl_fm** out);
+void rspl_fm_destroy(rspl_fm* h);
+/* Host matches in, results out: the host draws the subsets, the device solves, counts and accepts (three
+ * launches behind the upload), one wait. */
+int rspl_fm_solve(rspl_fm* h, const rspl_fm_problem* problems, int batch, rspl_fm_result* results);
+
+/* Device-resident: SuperPoint records [cap][259] (x, y = rows 1, 2) and device counts of both images, SuperGlue's
+ * device indices in, filtered indices out: copies of d_idx0 / d_idx1 with both ends of every rejected match set
+ * to -1 and everything else untouched (without a model: plain copies).  d_idx0_out / d_idx1_out drop into
+ * rspl_track_frame.d_idx0 / d_idx1, d_idx0_out into rspl_lines_stereo_device's d_match_idx.  The mutual matches
+ * are compacted in ascending index of image 0 (the DMatch order the subsets refer to).  Stream-ordered, no host
+ * synchronisation; one enqueue in flight per handle; stream may be NULL (the handle's own).  The subsets come
+ * from a table of raw RNG draws sized at create: it holds max_iters subsets and up to 256 redraws after a failed
+ * checkSubset for every match count (a handle that cannot hold 32 is refused); a frame that needs more ends its
+ * iterations there, where OpenCV would go on for up to 10000 attempts per iteration.  Keypoints past
+ * max_matches in either image are not considered and their index entries are copied unchanged. */
+typedef struct {
+  const double* d_features0;
+  const int32_t* d_n0;
+  const double* d_features1;
+  const int32_t* d_n1;
+  const int32_t* d_idx0;
+  const int32_t* d_idx1;
+  int32_t* d_idx0_out;
+  int32_t* d_idx1_out;
+  double threshold, confidence;
+} rspl_fm_frame;
+int rspl_fm_enqueue(rspl_fm* h, int batch, const rspl_fm_frame* frames, void* stream);
+/* Waits for the enqueue; inlier[] per compacted match (may be NULL; the caller sizes it for max_matches). */
+int rspl_fm_fetch(rspl_fm* h, rspl_fm_result* results);
+
+/* debug (parity tests) */
+/* host: the subsets `iters` iterations draw for `count` float-rounded pairs, idx [iters][7]; *n_found of them
+ * exist (getSubset gave up after 10000 attempts otherwise). */
+int rspl_fm_debug_subsets(int count, int iters, const double* points0, const double* points1, int32_t* idx,
+                          int* n_found);
+/* host mirror of the kernel's 7-point solver (csrc/fm_solve.hpp): p0, p1 [7][2] -> F [3][9], *n_models */
+int rspl_fm_debug_seven_point(const double* p0, const double* p1, double* F, int* n_models);
+/* frame `frame` of the last solve / fetched enqueue: the first min(max, iterations solved) iterations' model
+ * counts, inlier counts [max][3] and models [max][3][9]; returns how many, or a negative error */
+int rspl_fm_debug_hypotheses(rspl_fm* h, int frame, int max, int32_t* n_models, int32_t* counts, double* F);
+
 
 #ifdef __cplusplus
 }

@@ -559,6 +559,126 @@ _default_frame_cap = (0, 0)
 
 
 # ---------------------------------------------------------------------------
+# cv::findFundamentalMat(FM_RANSAC, 3, 0.99) as PointMatching::MatchingPoints calls it (point_matching.cc:34-45)
+# ---------------------------------------------------------------------------
+class FundamentalRansac:
+    """Owns one rspl_fm handle: the F-matrix RANSAC of the outlier rejection for a batch of frames, every
+    iteration's 7-point models solved and counted side by side, the sequential acceptance replayed on the
+    device.  ``solve`` takes host points; ``enqueue`` / ``fetch`` are the device-resident chain from
+    SuperGlue's device indices to filtered indices (``enqueue`` never waits for the device)."""
+
+    def __init__(self, max_batch=1, max_matches=1024, max_iters=1000, device=0):
+        self.max_batch, self.max_matches, self.max_iters = int(max_batch), int(max_matches), int(max_iters)
+        self._lib = capi.load()
+        self._h = C.c_void_p()
+        cfg = capi.FmConfig(self.max_batch, self.max_matches, self.max_iters, device)
+        capi.check(self._lib.rspl_fm_create(C.byref(cfg), C.byref(self._h)), "rspl_fm_create")
+        self._batch = 0
+
+    @staticmethod
+    def _results(R, masks, sizes=None):
+        out = []
+        for k, (r, m) in enumerate(zip(R, masks)):
+            n = sizes[k] if sizes is not None else int(np.count_nonzero(m != 255))
+            out.append(dict(n_inliers=r.n_inliers, hypotheses=r.hypotheses, F=np.array(r.F[:]),
+                            inlier=m[:n].copy()))
+        return out
+
+    def solve(self, problems, threshold=3.0, confidence=0.99):
+        """problems: list of (points0 [n, 2], points1 [n, 2]) pixels.  Returns one dict per problem:
+        n_inliers (-1: no model, nothing rejected), hypotheses (iterations evaluated), F [9], inlier [n] uint8."""
+        keep, P, R = [], [], []
+        for a, b in problems:
+            p0 = np.ascontiguousarray(a, np.float64).reshape(-1, 2)
+            p1 = np.ascontiguousarray(b, np.float64).reshape(-1, 2)
+            if p0.shape != p1.shape:
+                raise ValueError("FundamentalRansac.solve: points0 and points1 differ in length")
+            inl = np.zeros(max(p0.shape[0], 1), np.uint8)
+            keep.append((p0, p1, inl))
+            P.append(capi.FmProblem(p0.shape[0], p0.ctypes.data_as(C.POINTER(C.c_double)),
+                                    p1.ctypes.data_as(C.POINTER(C.c_double)), threshold, confidence))
+            r = capi.FmResult()
+            r.inlier = inl.ctypes.data_as(C.POINTER(C.c_uint8))
+            R.append(r)
+        Pa = (capi.FmProblem * max(len(P), 1))(*P)
+        Ra = (capi.FmResult * max(len(R), 1))(*R)
+        capi.check(self._lib.rspl_fm_solve(self._h, Pa, len(P), Ra), "rspl_fm_solve")
+        self._batch = 0
+        return self._results(Ra[:len(P)], [k[2] for k in keep], [k[0].shape[0] for k in keep])
+
+    def enqueue(self, frames, stream=None, threshold=3.0, confidence=0.99):
+        """frames: list of dicts with the device addresses ``d_features0``, ``d_n0``, ``d_features1``, ``d_n1``,
+        ``d_idx0``, ``d_idx1``, ``d_idx0_out``, ``d_idx1_out`` (ints or capi.DeviceBuffer)."""
+        F = (capi.FmFrame * max(len(frames), 1))()
+        for f, d in zip(F, frames):
+            for k in ("d_features0", "d_n0", "d_features1", "d_n1", "d_idx0", "d_idx1", "d_idx0_out", "d_idx1_out"):
+                v = d.get(k)
+                setattr(f, k, v.ptr if isinstance(v, capi.DeviceBuffer) else v)
+            f.threshold = d.get("threshold", threshold)
+            f.confidence = d.get("confidence", confidence)
+        capi.check(self._lib.rspl_fm_enqueue(self._h, len(frames), F, _stream_handle(stream)), "rspl_fm_enqueue")
+        self._batch = len(frames)
+
+    def fetch(self):
+        """Wait for the last enqueue.  One dict per frame as ``solve`` returns, inlier per compacted mutual
+        match (ascending index of image 0)."""
+        if self._batch == 0:
+            return []
+        R = (capi.FmResult * self._batch)()
+        masks = []
+        for r in R:
+            m = np.full(self.max_matches, 255, np.uint8)  # the library writes 0 / 1 for the frame's matches
+            r.inlier = m.ctypes.data_as(C.POINTER(C.c_uint8))
+            masks.append(m)
+        capi.check(self._lib.rspl_fm_fetch(self._h, R), "rspl_fm_fetch")
+        return self._results(R, masks)
+
+    def debug_hypotheses(self, frame=0, max_hyps=1000):
+        """the iterations solved for frame `frame` of the last solve / fetched enqueue: (n_models int32 [k],
+        counts int32 [k, 3] (-1 where there is no model), F [k, 3, 9])"""
+        nm = np.zeros(max_hyps, np.int32)
+        cnt = np.zeros((max_hyps, 3), np.int32)
+        F = np.zeros((max_hyps, 3, 9))
+        k = self._lib.rspl_fm_debug_hypotheses(self._h, frame, max_hyps, nm.ctypes.data, cnt.ctypes.data, F.ctypes.data)
+        if k < 0:
+            capi.check(k, "rspl_fm_debug_hypotheses")
+        nm, cnt, F = nm[:k], cnt[:k].copy(), F[:k].copy()
+        dead = np.arange(3)[None, :] >= nm[:, None]
+        cnt[dead] = -1
+        F[dead] = 0.0
+        return nm, cnt, F
+
+    @staticmethod
+    def debug_subsets(count, iters, points0, points1):
+        """host: the subsets `iters` iterations draw for `count` pairs, int32 [found, 7]"""
+        p0 = np.ascontiguousarray(points0, np.float64).reshape(-1, 2)
+        p1 = np.ascontiguousarray(points1, np.float64).reshape(-1, 2)
+        if p0.shape[0] != count or p1.shape[0] != count:
+            raise ValueError("debug_subsets: points do not match count")
+        idx = np.zeros((max(iters, 1), 7), np.int32)
+        n = C.c_int(0)
+        capi.check(capi.load().rspl_fm_debug_subsets(count, iters, p0.ctypes.data, p1.ctypes.data, idx.ctypes.data,
+                                                     C.byref(n)), "rspl_fm_debug_subsets")
+        return idx[:n.value].copy()
+
+    @staticmethod
+    def debug_seven_point(p0, p1):
+        """host mirror of the kernel's 7-point solver: [7, 2], [7, 2] -> models [k, 9]"""
+        a = np.ascontiguousarray(p0, np.float64).reshape(7, 2)
+        b = np.ascontiguousarray(p1, np.float64).reshape(7, 2)
+        F = np.zeros((3, 9))
+        n = C.c_int(0)
+        capi.check(capi.load().rspl_fm_debug_seven_point(a.ctypes.data, b.ctypes.data, F.ctypes.data, C.byref(n)),
+                   "rspl_fm_debug_seven_point")
+        return F[:n.value].copy()
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.rspl_fm_destroy(self._h)
+            self._h = C.c_void_p()
+
+
+# ---------------------------------------------------------------------------
 # SolvePnPWithCV (include/g2o_optimization/g2o_optimization.h:24, g2o_optimization.cc:402-461)
 # ---------------------------------------------------------------------------
 class PnP:

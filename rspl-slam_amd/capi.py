@@ -58,6 +58,8 @@ EXPORTS = [
     "rspl_rect_get_maps", "rspl_rect_set_maps", "rspl_rect_enqueue_device", "rspl_rect_pair",
     "rspl_rcf_debug_sizeof", "rspl_rcf_create", "rspl_rcf_destroy", "rspl_rcf_infer", "rspl_rcf_infer_device",
     "rspl_rcf_debug_logits", "rspl_rcf_debug_tile_rows", "rspl_rcf_profile", "rspl_rcf_stage_times",
+    "rspl_fm_create", "rspl_fm_destroy", "rspl_fm_solve", "rspl_fm_enqueue", "rspl_fm_fetch",
+    "rspl_fm_debug_subsets", "rspl_fm_debug_seven_point", "rspl_fm_debug_hypotheses",
 ]
 
 
@@ -109,6 +111,26 @@ class PnpProblem(C.Structure):
 class PnpResult(C.Structure):
     _fields_ = [("Rwc", C.c_double * 9), ("twc", C.c_double * 3), ("inlier", C.POINTER(C.c_uint8)),
                 ("n_inliers", C.c_int), ("hypotheses", C.c_int)]
+
+
+class FmConfig(C.Structure):
+    _fields_ = [("max_batch", C.c_int), ("max_matches", C.c_int), ("max_iters", C.c_int), ("device", C.c_int)]
+
+
+class FmProblem(C.Structure):
+    _fields_ = [("n", C.c_int), ("points0", C.POINTER(C.c_double)), ("points1", C.POINTER(C.c_double)),
+                ("threshold", C.c_double), ("confidence", C.c_double)]
+
+
+class FmResult(C.Structure):
+    _fields_ = [("inlier", C.POINTER(C.c_uint8)), ("n_inliers", C.c_int), ("hypotheses", C.c_int),
+                ("F", C.c_double * 9)]
+
+
+class FmFrame(C.Structure):
+    _fields_ = [("d_features0", C.c_void_p), ("d_n0", C.c_void_p), ("d_features1", C.c_void_p), ("d_n1", C.c_void_p),
+                ("d_idx0", C.c_void_p), ("d_idx1", C.c_void_p), ("d_idx0_out", C.c_void_p), ("d_idx1_out", C.c_void_p),
+                ("threshold", C.c_double), ("confidence", C.c_double)]
 
 
 class TrackConfig(C.Structure):
@@ -305,6 +327,16 @@ def load(path: pathlib.Path = LIB_PATH):
         lib.rspl_pnp_destroy.argtypes = [vp]
         lib.rspl_pnp_destroy.restype = None
         lib.rspl_pnp_debug_hypotheses.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    if hasattr(lib, "rspl_fm_create"):
+        lib.rspl_fm_create.argtypes = [C.POINTER(FmConfig), C.POINTER(vp)]
+        lib.rspl_fm_destroy.argtypes = [vp]
+        lib.rspl_fm_destroy.restype = None
+        lib.rspl_fm_solve.argtypes = [vp, vp, ip, vp]
+        lib.rspl_fm_enqueue.argtypes = [vp, ip, vp, vp]
+        lib.rspl_fm_fetch.argtypes = [vp, vp]
+        lib.rspl_fm_debug_subsets.argtypes = [ip, ip, vp, vp, vp, C.POINTER(C.c_int)]
+        lib.rspl_fm_debug_seven_point.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
+        lib.rspl_fm_debug_hypotheses.argtypes = [vp, ip, ip, vp, vp, vp]
     if hasattr(lib, "rspl_frame_create"):
         lib.rspl_frame_create.argtypes = [C.POINTER(FrameConfig), C.POINTER(vp)]
         lib.rspl_frame_optimize.argtypes = [vp, vp, ip, vp]

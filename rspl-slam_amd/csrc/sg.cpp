@@ -65,6 +65,7 @@ struct rspl_sg {
   unsigned long long calls = 0;
   int last_parity = 0;
   StageTimer timer;
+  rspl_fm* fm = nullptr;  // rspl_pm_match's outlier rejection, created on first use
 };
 
 namespace {
@@ -400,6 +401,7 @@ extern "C" int rspl_sg_create(const rspl_sg_config* cfg, const char* weights_pat
 
 extern "C" void rspl_sg_destroy(rspl_sg* s) {
   if (!s) return;
+  rspl_fm_destroy(s->fm);
 
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   s->arena.release();
@@ -610,7 +612,6 @@ extern "C" int rspl_sg_infer(rspl_sg* s, const double* f0, int n0, const double*
 extern "C" int rspl_pm_match(rspl_sg* s, const double* f0, int n0, const double* f1, int n1, rspl_dmatch* matches,
                              int capacity, int* n_matches, int outlier_rejection) {
   RSPL_CHECK_ARG(s && n_matches && (matches || capacity == 0), "rspl_pm_match: NULL argument");
-  RSPL_CHECK_ARG(!outlier_rejection, "outlier_rejection (cv::findFundamentalMat RANSAC) is not implemented");
   int rc = sg_host_run(s, f0, n0, f1, n1, 1);  // NormalizeKeypoints on device
   if (rc) return rc;
   const size_t nm = s->nmax;
@@ -632,6 +633,32 @@ extern "C" int rspl_pm_match(rspl_sg* s, const double* f0, int n0, const double*
       matches[k].distance = (float)d;
       k++;
     }
+  }
+  if (outlier_rejection && k > 0) {  // :34-45: findFundamentalMat(FM_RANSAC, 3, 0.99), the inliers kept in order
+    if (!s->fm) {
+      rspl_fm_config fc{};
+      fc.max_batch = 1;
+      fc.max_matches = s->cfg.max_keypoints;
+      fc.max_iters = 1000;
+      fc.device = s->cfg.device;
+      if (int rc2 = rspl_fm_create(&fc, &s->fm)) return rc2;
+    }
+    std::vector<double> p0(2 * (size_t)k), p1(2 * (size_t)k);
+    std::vector<uint8_t> keep(k);
+    for (int m = 0; m < k; m++) {
+      const double* r0 = f0 + 259 * (size_t)matches[m].query_idx;
+      const double* r1 = f1 + 259 * (size_t)matches[m].train_idx;
+      p0[2 * m] = r0[1]; p0[2 * m + 1] = r0[2];
+      p1[2 * m] = r1[1]; p1[2 * m + 1] = r1[2];
+    }
+    rspl_fm_problem pr{k, p0.data(), p1.data(), 3.0, 0.99};
+    rspl_fm_result fr{};
+    fr.inlier = keep.data();
+    if (int rc2 = rspl_fm_solve(s->fm, &pr, 1, &fr)) return rc2;
+    int kept = 0;
+    for (int m = 0; m < k; m++)
+      if (keep[m]) matches[kept++] = matches[m];
+    k = kept;
   }
   *n_matches = k;
   return RSPL_OK;
