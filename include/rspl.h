@@ -746,6 +746,53 @@ int rspl_lines_extract_wait_device(rspl_lines* h, double* d_lines, int capacity,
  * candidate, 1 none) for an H x W input, [H/2][W/2] each */
 int rspl_lines_debug_canny(rspl_lines* h, int H, int W, uint8_t* half, uint8_t* cls);
 
+/* The same detector, device-resident: `batch` (<= 2) u8 device images laid out as rspl_rcf_infer_device
+ * writes them (image b at d_images + b * pitch, row stride `stride`, both in bytes) -> d_segments
+ * [batch][capacity][4] float on the HALF image and d_counts [batch], both in device memory.  After the Canny
+ * classes, hysteresis, 8-connected component labels, the chain walk (one lane per component), the segment fit
+ * (one lane per chain) and the order by (seed, index within the chain) run as launches on `stream` (NULL: the
+ * handle's): the segments, their count, order and orientation are rspl_lines_detect's; the endpoints come
+ * from the device's fp64 atan2 / cos / sin and may differ from it by one float32 ulp.  Stream-ordered, never
+ * waits for the device (the first call, and a larger image than any before, allocate scratch); calls on one
+ * handle share that scratch and must be ordered among themselves.  d_counts[b] is the full count, the first
+ * `capacity` segments are written.  RSPL_E_ARG, before any device call, for: batch outside [1, 2], odd sizes
+ * or sizes below 4, stride < W, pitch < stride * (H - 1) + W, a half image whose two bitmasks
+ * (H/2 * ceil(W/2 / 32) * 8 bytes) exceed the 147456-byte LDS budget (1920 x 1080 needs 129600).  An image
+ * with more than 32768 edge pixels yields count 0 and status bit 1. */
+int rspl_lines_detect_device(rspl_lines* h, const uint8_t* d_images, int batch, int H, int W, size_t stride,
+                             size_t pitch, const rspl_fld_config* cfg, float* d_segments, int capacity,
+                             int32_t* d_counts, void* stream);
+/* the last rspl_lines_detect_device's overflow bits, OR-ed over its images, once its stream has completed:
+ * 1 more than 32768 edge pixels, 2 more segments than `capacity`, 4 an internal loop bound was hit */
+#define RSPL_FLD_ST_EDGE_PIXELS 1
+#define RSPL_FLD_ST_SEGMENTS 2
+#define RSPL_FLD_ST_LOGIC 4
+int rspl_lines_detect_status(rspl_lines* h, int* status);
+/* rspl_lines_extract_async with a device image: an event on `stream`, the device detector on the handle's own
+ * stream behind it, its count and segments (at most 4096) copied to pinned memory, rspl_line_extract on the
+ * worker.  Returns without waiting for the device; the image must stay valid until the job is waited for with
+ * rspl_lines_extract_wait / _wait_device, whose job_us then spans submit to the worker's end. */
+int rspl_lines_extract_async_device(rspl_lines* h, const uint8_t* d_image, int H, int W, size_t stride,
+                                    const rspl_fld_config* cfg, int do_merge, void* stream);
+/* debug (parity tests).  _hysteresis: a host class map [hh][hw] (2 strong, 0 candidate, 1 none) through the
+ * hysteresis kernel -> edge bytes (0 / 255) after the corner zeroing.  _chains: a host edge map through the
+ * label and walk kernels -> the chains sorted by seed: seeds [n] (pixel index), offsets [n + 1], points
+ * [offsets[n]][2] (x, y); *n_chains is set even when a capacity is exceeded (RSPL_E_CAPACITY).
+ * _fld_host: the device code's shared arithmetic on the CPU, with no device: a sequential walk of `edges`,
+ * then fit, filters and orientation against `half` -> segments as rspl_lines_detect orders them.
+ * _fld_stats: image b's counters of the last device detection: edge pixels, components, chains, segments,
+ * hysteresis passes, largest component, the walk's iteration count (its busiest lane), status.
+ * _fld_profile / _fld_stage_ms: with profiling on, events around the stages of each rspl_lines_detect_device;
+ * stage_ms waits for the last call and returns Canny classes, hysteresis, labels, walk, fit, order (ms). */
+int rspl_lines_debug_hysteresis(rspl_lines* h, const uint8_t* cls, int hh, int hw, uint8_t* edges);
+int rspl_lines_debug_chains(rspl_lines* h, const uint8_t* edges, int hh, int hw, int32_t* seeds, int32_t* offsets,
+                            int32_t* points, int cap_chains, int cap_points, int* n_chains);
+int rspl_lines_debug_fld_host(const uint8_t* half, const uint8_t* edges, int hh, int hw, const rspl_fld_config* cfg,
+                              float* segments, int capacity, int* n_out);
+int rspl_lines_debug_fld_stats(rspl_lines* h, int b, int32_t* stats);
+int rspl_lines_debug_fld_profile(rspl_lines* h, int enable);
+int rspl_lines_debug_fld_stage_ms(rspl_lines* h, float* ms);
+
 /* ------------------------------------------------------------------------ */
 /* The tracking step itself: MapBuilder::TrackFrame + FramePoseOptimization  */
 /* (src/map_builder.cc:448-611) for a batch of independent frames, from      */

@@ -48,6 +48,9 @@ EXPORTS = [
     "rspl_line_extract", "rspl_lines_create", "rspl_lines_destroy", "rspl_lines_assign", "rspl_lines_match",
     "rspl_lines_stereo", "rspl_lines_stereo_device", "rspl_lines_status", "rspl_lines_detect",
     "rspl_lines_debug_canny",
+    "rspl_lines_detect_device", "rspl_lines_detect_status", "rspl_lines_extract_async_device",
+    "rspl_lines_debug_hysteresis", "rspl_lines_debug_chains", "rspl_lines_debug_fld_host",
+    "rspl_lines_debug_fld_stats", "rspl_lines_debug_fld_profile", "rspl_lines_debug_fld_stage_ms",
     "rspl_track_create", "rspl_track_destroy", "rspl_track_set_keyframe", "rspl_track_enqueue", "rspl_track_fetch",
     "rspl_track_debug_stage", "rspl_track_keyframe_table",
     "rspl_track_enable_lines", "rspl_track_set_keyframe_lines", "rspl_track_enqueue_ext", "rspl_track_fetch_ext",

@@ -4,7 +4,9 @@ Mirrors the reference's free functions and LineDetector (include/line_processor.
 
   LineDetector              createFastLineDetector(config) + LineExtractor(image) (line_processor.cc:
                             455-490): cv::resize(0.5) + FLD (restated: GPU resize / Sobel / Canny
-                            classification, host hysteresis / chaining / fitting), then the merges
+                            classification, host hysteresis / chaining / fitting), then the merges;
+                            detect_device / submit_device: the same detector on a device image (the RCF
+                            network's output), hysteresis / chaining / fitting as HIP kernels, stream-ordered
   LineExtractor(segments)   LineDetector::LineExtractor after fld->detect (line_processor.cc:460-490):
                             the x2 scale and the two MergeLines / FilterShortLines passes (host C++)
   AssignPointsToLines       line_processor.cc:163-216 (GPU) -> list of {point index: distance}
@@ -60,6 +62,16 @@ def _declare(lib):
     lib.rspl_lines_extract_async.argtypes = [vp, _u8p, ip, ip, ip, C.POINTER(FldConfig), ip]
     lib.rspl_lines_extract_wait.argtypes = [vp, _dp, ip, C.POINTER(ip), _dp]
     lib.rspl_lines_extract_wait_device.argtypes = [vp, vp, ip, C.POINTER(ip), _dp, vp]
+    sz = C.c_size_t
+    lib.rspl_lines_detect_device.argtypes = [vp, vp, ip, ip, ip, sz, sz, C.POINTER(FldConfig), vp, ip, vp, vp]
+    lib.rspl_lines_detect_status.argtypes = [vp, C.POINTER(ip)]
+    lib.rspl_lines_extract_async_device.argtypes = [vp, vp, ip, ip, sz, C.POINTER(FldConfig), ip, vp]
+    lib.rspl_lines_debug_hysteresis.argtypes = [vp, _u8p, ip, ip, _u8p]
+    lib.rspl_lines_debug_chains.argtypes = [vp, _u8p, ip, ip, _i32p, _i32p, _i32p, ip, ip, C.POINTER(ip)]
+    lib.rspl_lines_debug_fld_host.argtypes = [_u8p, _u8p, ip, ip, C.POINTER(FldConfig), _fp, ip, C.POINTER(ip)]
+    lib.rspl_lines_debug_fld_stats.argtypes = [vp, ip, _i32p]
+    lib.rspl_lines_debug_fld_profile.argtypes = [vp, ip]
+    lib.rspl_lines_debug_fld_stage_ms.argtypes = [vp, _fp]
     lib._rspl_lines_declared = True
     return lib
 
@@ -101,6 +113,41 @@ def relation_to_csr(relation: Sequence[Dict[int, float]]) -> Tuple[np.ndarray, n
 
 def csr_to_relation(off, idx, dist) -> List[Dict[int, float]]:
     return [{int(idx[e]): float(dist[e]) for e in range(off[i], off[i + 1])} for i in range(len(off) - 1)]
+
+
+FLD_ST_EDGE_PIXELS, FLD_ST_SEGMENTS, FLD_ST_LOGIC = 1, 2, 4  # rspl_lines_detect_status bits
+FLD_MAX_BATCH = 2            # images per detect_device call
+FLD_MAX_EDGE_PIXELS = 32768  # per image; more yields count 0 and FLD_ST_EDGE_PIXELS
+FLD_MASK_LDS_BYTES = 147456  # H/2 * ceil(W/2 / 32) * 8 must not exceed it
+FLD_STATS = ("edge_pixels", "components", "chains", "segments", "hysteresis_passes", "largest_component",
+             "walk_iterations", "status")
+FLD_STAGES = ("canny_classes", "hysteresis", "labels", "walk", "fit", "order")
+
+
+def _dev(v):
+    return v.ptr if isinstance(v, capi.DeviceBuffer) else v
+
+
+def _stream(s):
+    return s.handle if isinstance(s, capi.Stream) else s
+
+
+def debug_fld_host(half: np.ndarray, edges: np.ndarray, length_threshold=10, distance_threshold=1.414213562,
+                   capacity: int = 16384) -> np.ndarray:
+    """rspl_lines_debug_fld_host: the device detector's shared arithmetic on the CPU (no device needed): a
+    sequential walk of the edge map `edges` (after hysteresis and corner zeroing), then fit, filters and
+    orientation against the half image -> segments [n][4] float32"""
+    lib = _declare(capi.load())
+    half = np.ascontiguousarray(half, np.uint8)
+    edges = np.ascontiguousarray(edges, np.uint8)
+    assert half.shape == edges.shape and half.ndim == 2
+    cfg = FldConfig(length_threshold, distance_threshold, 0.0, 0.0, 3)
+    seg = np.zeros((max(1, capacity), 4), np.float32)
+    n = C.c_int()
+    capi.check(lib.rspl_lines_debug_fld_host(half.ctypes.data_as(_u8p), edges.ctypes.data_as(_u8p), half.shape[0],
+                                             half.shape[1], C.byref(cfg), seg.ctypes.data_as(_fp), capacity,
+                                             C.byref(n)), "rspl_lines_debug_fld_host")
+    return seg[: n.value].copy()
 
 
 class LineMatcher:
@@ -253,3 +300,63 @@ class LineDetector:
         capi.check(rc, "rspl_lines_extract_wait_device")
         return n.value, us.value / 1e3
 
+    # --- the detector on the device (rspl_lines_detect_device and its parity hooks) ---
+    def detect_device(self, d_images, batch: int, H: int, W: int, stride: int, pitch: int, d_segments, capacity: int,
+                      d_counts, stream=None):
+        """`batch` (<= FLD_MAX_BATCH) device images (image b at d_images + b * pitch, row stride `stride`, as
+        RCF.infer_device writes them) -> d_segments [batch][capacity][4] float32 on the half image and d_counts
+        [batch] int32, both device memory; stream-ordered, never waits for the device"""
+        capi.check(self._lib.rspl_lines_detect_device(self._h, _dev(d_images), int(batch), int(H), int(W), stride,
+                                                      pitch, C.byref(self.cfg), _dev(d_segments), int(capacity),
+                                                      _dev(d_counts), _stream(stream)), "rspl_lines_detect_device")
+
+    def detect_status(self) -> int:
+        """the last detect_device's overflow bits (FLD_ST_*), once its stream has completed"""
+        st = C.c_int()
+        capi.check(self._lib.rspl_lines_detect_status(self._h, C.byref(st)), "rspl_lines_detect_status")
+        return st.value
+
+    def submit_device(self, d_image, H: int, W: int, stride: int, stream=None):
+        """submit() with a device image that `stream` produces: the device detector runs on the handle's own
+        stream behind an event on `stream`, the merges on the worker; wait() / wait_device() deliver the lines.
+        The image must stay valid until then."""
+        self._job_img = d_image
+        capi.check(self._lib.rspl_lines_extract_async_device(self._h, _dev(d_image), int(H), int(W), stride,
+                                                             C.byref(self.cfg), int(self.do_merge), _stream(stream)),
+                   "rspl_lines_extract_async_device")
+
+    def debug_hysteresis(self, cls: np.ndarray) -> np.ndarray:
+        """a class map (2 strong, 0 candidate, 1 none) through the hysteresis kernel -> edges (0 / 255) after the
+        corner zeroing"""
+        cls = np.ascontiguousarray(cls, np.uint8)
+        out = np.zeros_like(cls)
+        capi.check(self._lib.rspl_lines_debug_hysteresis(self._h, cls.ctypes.data_as(_u8p), cls.shape[0], cls.shape[1],
+                                                         out.ctypes.data_as(_u8p)), "rspl_lines_debug_hysteresis")
+        return out
+
+    def debug_chains(self, edges: np.ndarray):
+        """an edge map through the label and walk kernels -> [(seed pixel index, points [n][2] (x, y))] by seed"""
+        edges = np.ascontiguousarray(edges, np.uint8)
+        cap = max(1, int(np.count_nonzero(edges)))
+        seeds, off, pts = np.zeros(cap, np.int32), np.zeros(cap + 1, np.int32), np.zeros((cap, 2), np.int32)
+        n = C.c_int()
+        capi.check(self._lib.rspl_lines_debug_chains(self._h, edges.ctypes.data_as(_u8p), edges.shape[0],
+                                                     edges.shape[1], seeds.ctypes.data_as(_i32p),
+                                                     off.ctypes.data_as(_i32p), pts.ctypes.data_as(_i32p), cap, cap,
+                                                     C.byref(n)), "rspl_lines_debug_chains")
+        return [(int(seeds[k]), pts[off[k]:off[k + 1]].copy()) for k in range(n.value)]
+
+    def debug_fld_stats(self, b: int = 0) -> dict:
+        st = np.zeros(8, np.int32)
+        capi.check(self._lib.rspl_lines_debug_fld_stats(self._h, int(b), st.ctypes.data_as(_i32p)),
+                   "rspl_lines_debug_fld_stats")
+        return dict(zip(FLD_STATS, (int(v) for v in st)))
+
+    def debug_fld_profile(self, enable: bool = True):
+        capi.check(self._lib.rspl_lines_debug_fld_profile(self._h, int(enable)), "rspl_lines_debug_fld_profile")
+
+    def debug_fld_stage_ms(self) -> dict:
+        ms = np.zeros(6, np.float32)
+        capi.check(self._lib.rspl_lines_debug_fld_stage_ms(self._h, ms.ctypes.data_as(_fp)),
+                   "rspl_lines_debug_fld_stage_ms")
+        return dict(zip(FLD_STAGES, (float(v) for v in ms)))
