@@ -3,7 +3,11 @@ orc_frame_opt) on the same inputs: identical round counts, inlier counts and inl
 poses within 1e-9 m / rad, per-round final chi2 within rtol 1e-9.  LM iteration counts are NOT
 compared: once a round has converged, g2o's stop test (rho == 0, or 10 rejected trials) is
 decided by the last ulp of chi2, which the GPU's reduction tree and the host's sequential sum
-round differently -- parity is judged on the optimum, as SURVEY.md section 8c states."""
+round differently -- parity is judged on the optimum, as SURVEY.md section 8c states.
+Every problem here is a generic synthetic.frame_problem.  The degenerate inputs (no inlier at all, points
+behind the camera, a poor seed, a rank-deficient system) and the kernel's variants side by side (all four
+frame_opt_kernel<LDS, NW> instantiations, 512 | 513 edges, 256 | 257 frames, the staging loop's tails,
+empty and tiny frames on the global path) are in tests/test_gpu_pose_edges.py, to the same _compare."""
 import numpy as np
 import pytest
 

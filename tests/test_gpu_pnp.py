@@ -8,7 +8,11 @@ inputs.  Two oracles:
   * an INDEPENDENT restatement (oracle.pnp(independent=True): the classic cyclic Jacobi) -- the RANSAC
     outcome (inlier set) identical and the refined optimum within 1e-7 / 1e-6 m.
 Parity at the OpenCV boundary (cvSVD, solvePnPRansac) is unpinned: OpenCV is not vendored in the
-reference."""
+reference.
+Every problem here is a generic synthetic.pnp_problem (no failed minimal solve, 100 iterations, one
+frame's hypotheses).  Degenerate geometry (coplanar and repeated points, nothing but outliers), the
+hypotheses of batch frames behind frame 0, other iteration counts and the counts at the kernels'
+strides are in tests/test_gpu_pose_edges.py, to the same _compare."""
 import numpy as np
 import pytest
 
