@@ -32,6 +32,7 @@
 #include "ba_kernels.hpp"
 #include "common.hpp"
 #include "ba_stage.hpp"
+#include "se3_host.hpp"
 
 using namespace rspl;
 
@@ -155,7 +156,6 @@ int allreduce(rspl_ba* b, double* d, size_t n) {
   return RSPL_OK;
 }
 
-inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // per-call upload layout (staging call region == device call buffer)
 struct CallLayout {
@@ -358,36 +358,7 @@ int grow_device(rspl_ba* b, T*& buf, size_t& cap, size_t need, size_t min_cap, u
   return RSPL_OK;
 }
 
-struct Se3h {  // host SE3Quat (w x y z, t)
-  double q[4], t[3];
-};
-
-void q_to_R(const double* q, double* R) {
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x;
-  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-
-void normalize(Se3h& T) {
-  if (T.q[0] < 0)
-    for (double& v : T.q) v = -v;
-  const double n = std::sqrt(T.q[0] * T.q[0] + T.q[1] * T.q[1] + T.q[2] * T.q[2] + T.q[3] * T.q[3]);
-  for (double& v : T.q) v /= n;
-}
-
-Se3h inverse(const Se3h& T) {  // SE3Quat::inverse
-  Se3h r;
-  r.q[0] = T.q[0]; r.q[1] = -T.q[1]; r.q[2] = -T.q[2]; r.q[3] = -T.q[3];
-  double R[9];
-  q_to_R(r.q, R);
-  for (int i = 0; i < 3; i++) r.t[i] = -(R[3 * i] * T.t[0] + R[3 * i + 1] * T.t[1] + R[3 * i + 2] * T.t[2]);
-  normalize(r);
-  return r;
-}
+using se3h::Se3h;
 
 // RSPL_BA_PROF: one traced trial per call -> one stderr line of in-kernel spans (us, from the
 // device's 100 MHz wall clock): pair_chunk first..last block start, span; gap to the solve;

@@ -36,6 +36,8 @@ int cu_mask(int reserve_cus, bool reserved_only, std::vector<uint32_t>& mask);
     }                                \
   } while (0)
 
+inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
+
 // One hipMalloc per handle; sub-allocations are 256-byte aligned.
 struct Arena {
   char* base = nullptr;
@@ -52,7 +54,7 @@ struct Arena {
   }
   template <typename T>
   T* take(size_t count) {
-    size_t off = (used + 255) & ~size_t(255);
+    size_t off = al256(used);
     used = off + count * sizeof(T);
     if (used > size) return nullptr;
     return reinterpret_cast<T*>(base + off);
@@ -63,12 +65,53 @@ struct Arena {
   }
 };
 
-// Size-only pass of the same carving, so arenas are allocated exactly once.
+// Arena's host-mapped twin: one pinned, coherent block per handle that the device reads and writes through
+// its own address of it.  take() hands back both addresses of a piece.  The pieces share one allocation: only
+// kernels (and the host) may be given them, never a HIP call that wants an allocation's base.
+struct PinnedArena {
+  char *base = nullptr, *dev = nullptr;
+  size_t size = 0, used = 0;
+  int reserve(size_t bytes) {
+    size = bytes;
+    used = 0;
+    if (hipHostMalloc((void**)&base, bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+      set_error("hipHostMalloc(%zu) failed", bytes);
+      base = nullptr;
+      return RSPL_E_DEVICE;
+    }
+    if (hipHostGetDevicePointer((void**)&dev, base, 0) != hipSuccess) {
+      set_error("hipHostGetDevicePointer failed");
+      release();
+      return RSPL_E_DEVICE;
+    }
+    return RSPL_OK;
+  }
+  template <typename T, typename D>
+  T* take(size_t count, D** dev_out) {  // D: T or const T
+    size_t off = al256(used);
+    used = off + count * sizeof(T);
+    if (used > size) return nullptr;
+    *dev_out = reinterpret_cast<T*>(dev + off);
+    return reinterpret_cast<T*>(base + off);
+  }
+  void release() {
+    if (base) (void)hipHostFree(base);
+    base = dev = nullptr;
+  }
+};
+
+// Size-only pass of the same carving (either arena's), so each is allocated exactly once: run the carve with
+// a Sizer, reserve(used), run it again with the arena.
 struct Sizer {
   size_t used = 0;
   template <typename T>
-  void take(size_t count) {
-    used = ((used + 255) & ~size_t(255)) + count * sizeof(T);
+  T* take(size_t count) {
+    used = al256(used) + count * sizeof(T);
+    return nullptr;
+  }
+  template <typename T, typename D>
+  T* take(size_t count, D**) {
+    return take<T>(count);
   }
 };
 

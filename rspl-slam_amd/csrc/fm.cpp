@@ -12,6 +12,7 @@
 #include "common.hpp"
 #include "fm_kernels.hpp"
 #include "fm_solve.hpp"
+#include "ransac.hpp"
 
 using namespace rspl;
 
@@ -20,8 +21,9 @@ struct rspl_fm {
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;
   Arena arena;
+  PinnedArena pinned;
   fm::Args a{};
-  // host-mapped staging of rspl_fm_solve's upload, with the device pointers the copy kernel reads
+  // host-mapped (pieces of `pinned`) staging of rspl_fm_solve's upload, with the device pointers the copy kernel reads
   fm::Desc *s_desc = nullptr, *s_desc_dev = nullptr;
   double *s_p0 = nullptr, *s_p0_dev = nullptr, *s_p1 = nullptr, *s_p1_dev = nullptr;
   int32_t *s_sub = nullptr, *s_sub_dev = nullptr;
@@ -35,24 +37,6 @@ struct rspl_fm {
 
 namespace {
 
-struct Count {  // the size-only pass of the arena carving
-  size_t used = 0;
-  template <typename T>
-  T* take(size_t count) {
-    used = ((used + 255) & ~size_t(255)) + count * sizeof(T);
-    return nullptr;
-  }
-};
-
-template <typename T>
-int mapped(T** host, T** dev, size_t count) {
-  if (hipHostMalloc((void**)host, sizeof(T) * std::max<size_t>(count, 1), hipHostMallocMapped | hipHostMallocCoherent) !=
-          hipSuccess ||
-      hipHostGetDevicePointer((void**)dev, *host, 0) != hipSuccess)
-    return RSPL_E_DEVICE;
-  return RSPL_OK;
-}
-
 // RANSACPointSetRegistrator::getSubset over cv::RNG::next for every iteration: 7 distinct indices, a subset
 // failing checkSubset is drawn again from the continuing stream, at most kMaxAttempts times.  p0 / p1: the
 // float-rounded pairs.  Returns the subsets found (the sequence ends where getSubset gives up).
@@ -63,15 +47,9 @@ int subsets(int count, int iters, const double* p0, const double* p1, int32_t* i
     bool found = false;
     for (int attempt = 0; attempt < fm::kMaxAttempts && !found; attempt++) {
       double s0[14], s1[14];
+      ransac::draw_subset<7>(s, count, o);
       for (int i = 0; i < 7; i++) {
-        int v;
-        for (;;) {
-          v = (int)(fm::rng_next(s) % (unsigned)count);
-          bool dup = false;
-          for (int j = 0; j < i; j++) dup |= o[j] == v;
-          if (!dup) break;
-        }
-        o[i] = v;
+        const int v = o[i];
         s0[2 * i] = p0[2 * v]; s0[2 * i + 1] = p0[2 * v + 1];
         s1[2 * i] = p1[2 * v]; s1[2 * i + 1] = p1[2 * v + 1];
       }
@@ -80,32 +58,6 @@ int subsets(int count, int iters, const double* p0, const double* p1, int32_t* i
     if (!found) return h;
   }
   return iters;
-}
-
-// The draws the first `want` subsets of `count` correspondences consume when none fails checkSubset, or -1
-// when the table d ends first; *fit = the subsets that do fit, *fit_draws their draws.
-int draws_needed(const std::vector<uint32_t>& d, int count, int want, int* fit, int* fit_draws) {
-  size_t pos = 0;
-  *fit = 0;
-  *fit_draws = 0;
-  for (int h = 0; h < want; h++) {
-    int o[7];
-    for (int i = 0; i < 7; i++) {
-      for (;;) {
-        if (pos >= d.size()) return -1;
-        const int v = (int)(d[pos++] % (unsigned)count);
-        bool dup = false;
-        for (int j = 0; j < i; j++) dup |= o[j] == v;
-        if (!dup) {
-          o[i] = v;
-          break;
-        }
-      }
-    }
-    *fit = h + 1;
-    *fit_draws = (int)pos;
-  }
-  return (int)pos;
 }
 
 bool good_ransac(double threshold, double confidence) {
@@ -141,16 +93,12 @@ extern "C" int rspl_fm_create(const rspl_fm_config* cfg, rspl_fm** out) {
   // reject the most duplicates (count 8: ~13.7 draws per subset); where max_iters + kRedrawSlack subsets do
   // not fit the kernel's LDS tables, the slack shrinks, and below kMinSlack the handle is refused.
   const int B = cfg->max_batch, K = cfg->max_matches;
-  std::vector<uint32_t> draws(fm::kDrawCap);
-  {
-    uint64_t s = (uint64_t)-1;
-    for (uint32_t& d : draws) d = fm::rng_next(s);
-  }
+  std::vector<uint32_t> draws = ransac::raw_draws(fm::kDrawCap);
   std::vector<int32_t> need(K + 1, 0);
   int nd = 0;
   for (int c = 8; c <= K; c++) {
     int fit = 0, fit_draws = 0;
-    const int all = draws_needed(draws, c, cfg->max_iters + fm::kRedrawSlack, &fit, &fit_draws);
+    const int all = ransac::draws_needed<7>(draws, c, cfg->max_iters + fm::kRedrawSlack, &fit, &fit_draws);
     RSPL_CHECK_ARG(all >= 0 || fit >= cfg->max_iters + fm::kMinSlack,
                    "rspl_fm_create: %d iterations of %d matches need more than %d RNG draws", cfg->max_iters, c,
                    fm::kDrawCap);
@@ -165,7 +113,14 @@ extern "C" int rspl_fm_create(const rspl_fm_config* cfg, rspl_fm** out) {
   fm::Args& a = h->a;
   uint32_t* d_draws = nullptr;
   int32_t* d_need = nullptr;
-  auto carve = [&](auto& A) {
+  auto carve = [&](auto& A, auto& P) {
+    h->s_desc = P.template take<fm::Desc>(B, &h->s_desc_dev);
+    h->s_p0 = P.template take<double>(2 * E, &h->s_p0_dev);
+    h->s_p1 = P.template take<double>(2 * E, &h->s_p1_dev);
+    h->s_sub = P.template take<int32_t>(7 * S, &h->s_sub_dev);
+    h->params = P.template take<fm::Param>(B, &a.host_params);
+    h->out = P.template take<fm::Out>(B, &a.out);
+    h->inl = P.template take<uint8_t>(E, &a.inl);
     d_draws = A.template take<uint32_t>(draws.size());
     d_need = A.template take<int32_t>(need.size());
     a.frames = A.template take<fm::Desc>(B);
@@ -179,20 +134,17 @@ extern "C" int rspl_fm_create(const rspl_fm_config* cfg, rspl_fm** out) {
     a.match0 = A.template take<int32_t>(E);
     a.match1 = A.template take<int32_t>(E);
   };
-  Count sz;
-  carve(sz);
+  Sizer sz, psz;
+  carve(sz, psz);
   int rc = h->arena.reserve(sz.used + 256);
+  if (!rc) rc = h->pinned.reserve(psz.used + 256);
   if (rc) {
-    delete h;
+    rspl_fm_destroy(h);
     return rc;
   }
-  carve(h->arena);
+  carve(h->arena, h->pinned);
   bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreateWithFlags(&h->done, hipEventDisableTiming) == hipSuccess &&
-            mapped(&h->s_desc, &h->s_desc_dev, B) == RSPL_OK && mapped(&h->s_p0, &h->s_p0_dev, 2 * E) == RSPL_OK &&
-            mapped(&h->s_p1, &h->s_p1_dev, 2 * E) == RSPL_OK && mapped(&h->s_sub, &h->s_sub_dev, 7 * S) == RSPL_OK &&
-            mapped(&h->params, const_cast<fm::Param**>(&a.host_params), B) == RSPL_OK &&
-            mapped(&h->out, &a.out, B) == RSPL_OK && mapped(&h->inl, &a.inl, E) == RSPL_OK;
+            hipEventCreateWithFlags(&h->done, hipEventDisableTiming) == hipSuccess;
   // (the scratch is zeroed once so that a debug read-back of slots no kernel wrote is defined)
   ok = ok && hipMemset(h->arena.base, 0, h->arena.used) == hipSuccess &&
        hipMemcpy(d_draws, draws.data(), sizeof(uint32_t) * draws.size(), hipMemcpyHostToDevice) == hipSuccess &&
@@ -216,16 +168,7 @@ extern "C" void rspl_fm_destroy(rspl_fm* h) {
   if (h->pending && h->done) (void)hipEventSynchronize(h->done);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   h->arena.release();
-  auto drop = [](auto* p) {
-    if (p) (void)hipHostFree(p);
-  };
-  drop(h->s_desc);
-  drop(h->s_p0);
-  drop(h->s_p1);
-  drop(h->s_sub);
-  drop(h->params);
-  drop(h->out);
-  drop(h->inl);
+  h->pinned.release();
   if (h->done) (void)hipEventDestroy(h->done);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;

@@ -11,6 +11,7 @@
 // sequential loop would have evaluated, so the result is the sequential one for every n.
 #include "fm_kernels.hpp"
 #include "fm_solve.hpp"
+#include "ransac.hpp"
 #include "wave_reduce.hpp"
 
 namespace rspl {
@@ -20,30 +21,8 @@ namespace {
 constexpr int T = 256, NW = 4;
 constexpr int kCountWaves = 4;  // iterations (one wave each) per workgroup of fm_count_kernel
 
+using ransac::subset_at;
 using wave::lanes_below;
-
-// RANSACPointSetRegistrator::getSubset started at draw k of the (already reduced % count) stream dv[0, nd):
-// 7 distinct values, a duplicate draws again.  Returns the draws consumed, 0 when the table ends first.
-__device__ __forceinline__ int subset_at(const unsigned short* dv, int nd, int k, int (&o)[7]) {
-  int pos = k;
-#pragma unroll
-  for (int i = 0; i < 7; i++) o[i] = -1;
-#pragma unroll
-  for (int i = 0; i < 7; i++) {
-    for (;;) {
-      if (pos >= nd) return 0;
-      const int v = dv[pos++];
-      bool dup = false;
-#pragma unroll
-      for (int j = 0; j < 7; j++) dup |= j < i && o[j] == v;
-      if (!dup) {
-        o[i] = v;
-        break;
-      }
-    }
-  }
-  return pos - k;
-}
 
 __device__ __forceinline__ void load_subset_points(const double* p, const int (&o)[7], double (&s)[14]) {
 #pragma unroll
@@ -75,11 +54,7 @@ __global__ __launch_bounds__(T) void fm_gather_kernel(Args a) {
   int base = 0;
   for (int c = 0; c < n0; c += T) {
     const int i = c + tid;
-    int j = -1;
-    if (i < n0) {
-      const int jj = P.idx0[i];
-      if (jj >= 0 && jj < n1 && P.idx1[jj] == i) j = jj;
-    }
+    const int j = i < n0 ? ransac::mutual_partner(P.idx0, P.idx1, i, n1) : -1;
     const unsigned long long mk = __ballot(j >= 0);
     if (lane == 0) wtot[wv] = __popcll(mk);
     __syncthreads();
@@ -235,7 +210,7 @@ __global__ __launch_bounds__(T) void fm_accept_kernel(Args a, int write_back) {
           best = h;
           best_m = m;
           best_cnt = c;
-          niters = update_num_iters(D.confidence, (double)(n - c) / n, kModelPoints, niters);
+          niters = ransac::update_num_iters(D.confidence, (double)(n - c) / n, (double)kModelPoints, niters);
         }
       }
     }

@@ -60,12 +60,6 @@ struct Args {
   int32_t* match1;
 };
 
-// cv::RNG::next (multiply-with-carry), seeded (uint64)-1 by RANSACPointSetRegistrator::run
-inline unsigned rng_next(uint64_t& s) {
-  s = (uint64_t)(unsigned)s * 4164903690u + (unsigned)(s >> 32);
-  return (unsigned)s;
-}
-
 hipError_t gather(const Args& a, int batch, hipStream_t s);                 // device-resident path only
 hipError_t solve(const Args& a, int batch, bool write_back, hipStream_t s);  // hypotheses | counts | acceptance
 

@@ -262,17 +262,5 @@ RSPL_FM_HD int seven_point(const double* p0, const double* p1, double* w, double
   return n;
 }
 
-// RANSACUpdateNumIters
-RSPL_FM_HD int update_num_iters(double p, double ep, int model_points, int max_iters) {
-  p = fmin(fmax(p, 0.), 1.);
-  ep = fmin(fmax(ep, 0.), 1.);
-  double num = fmax(1. - p, DBL_MIN);
-  double denom = 1. - pow(1. - ep, (double)model_points);
-  if (denom < DBL_MIN) return 0;
-  num = log(num);
-  denom = log(denom);
-  return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)rint(num / denom);
-}
-
 }  // namespace fm
 }  // namespace rspl

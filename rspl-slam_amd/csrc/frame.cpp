@@ -10,6 +10,7 @@
 
 #include "common.hpp"
 #include "frame_kernels.hpp"
+#include "se3_host.hpp"
 
 using namespace rspl;
 
@@ -17,15 +18,16 @@ struct rspl_frame {
   rspl_frame_config cfg{};
   hipStream_t stream = nullptr;
   Arena arena;
+  PinnedArena pinned;
   // device: upload region (descriptors | edges | inlier-in, laid out per call like the
   // staging buffer), error / level / inlier scratch
   char* up = nullptr;
   uint8_t *level = nullptr, *inl = nullptr;
   double* err = nullptr;
-  // pinned upload staging (descs | edges | inlier-in), mirrors the device layout
-  char* stage = nullptr;      // pinned, host-mapped staging of the upload region
-  char* stage_dev = nullptr;  // its device pointer (the upload kernel reads it)
-  // host-mapped results
+  // pieces of `pinned`: the upload staging (descs | edges | inlier-in), mirrors the device layout
+  char* stage = nullptr;
+  char* stage_dev = nullptr;  // its device pointer (the kernels read it)
+  // ... and the results
   frame::Out* out = nullptr;
   frame::Out* out_dev = nullptr;
   uint8_t* inl_out = nullptr;
@@ -34,38 +36,7 @@ struct rspl_frame {
 
 namespace {
 
-struct Q {  // SE3Quat (w x y z, t), host side
-  double q[4], t[3];
-};
-
-void q_to_R(const double* q, double* R) {
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x;
-  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-
-void normalize(Q& T) {  // SE3Quat::normalizeRotation
-  if (T.q[0] < 0)
-    for (double& v : T.q) v = -v;
-  const double n = std::sqrt(T.q[0] * T.q[0] + T.q[1] * T.q[1] + T.q[2] * T.q[2] + T.q[3] * T.q[3]);
-  for (double& v : T.q) v /= n;
-}
-
-Q inverse(const Q& T) {  // SE3Quat::inverse
-  Q r;
-  r.q[0] = T.q[0]; r.q[1] = -T.q[1]; r.q[2] = -T.q[2]; r.q[3] = -T.q[3];
-  double R[9];
-  q_to_R(r.q, R);
-  for (int i = 0; i < 3; i++) r.t[i] = -(R[3 * i] * T.t[0] + R[3 * i + 1] * T.t[1] + R[3 * i + 2] * T.t[2]);
-  normalize(r);
-  return r;
-}
-
-inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
+using Q = se3h::Se3h;  // SE3Quat (w x y z, t), host side
 
 struct Layout {  // staging == device upload region
   size_t desc, edges, inl, bytes;
@@ -88,29 +59,29 @@ extern "C" int rspl_frame_create(const rspl_frame_config* cfg, rspl_frame** out)
   h->cfg = *cfg;
   const int B = cfg->max_batch, E = std::max(cfg->max_edges, 1);
   const Layout lay(B, E);
-  const size_t scratch = al256(sizeof(double) * 4 * (size_t)E) + 2 * al256(E);
-  int rc = h->arena.reserve(lay.bytes + scratch + 1024);
+  auto carve = [&](auto& A, auto& P) {
+    // the upload region first (one copy lands descs, edges and inlier flags), then scratch
+    h->up = A.template take<char>(lay.bytes);
+    h->err = A.template take<double>(4 * (size_t)E);
+    h->level = A.template take<uint8_t>(E);
+    h->inl = A.template take<uint8_t>(E);
+    h->stage = P.template take<char>(lay.bytes, &h->stage_dev);
+    h->out = P.template take<frame::Out>(B, &h->out_dev);
+    h->inl_out = P.template take<uint8_t>(E, &h->inl_out_dev);
+  };
+  Sizer sz, psz;
+  carve(sz, psz);
+  int rc = h->arena.reserve(sz.used + 256);
+  if (!rc) rc = h->pinned.reserve(psz.used + 256);
+  if (!rc && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+    set_error("rspl_frame_create: stream creation failed");
+    rc = RSPL_E_DEVICE;
+  }
   if (rc) {
-    delete h;
+    rspl_frame_destroy(h);
     return rc;
   }
-  // the upload region first (one copy lands descs, edges and inlier flags), then scratch
-  h->up = h->arena.take<char>(lay.bytes);
-  h->err = h->arena.take<double>(4 * (size_t)E);
-  h->level = h->arena.take<uint8_t>(E);
-  h->inl = h->arena.take<uint8_t>(E);
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipHostMalloc((void**)&h->stage, lay.bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&h->stage_dev, h->stage, 0) != hipSuccess ||
-      hipHostMalloc((void**)&h->out, sizeof(frame::Out) * B, hipHostMallocMapped | hipHostMallocCoherent) !=
-          hipSuccess ||
-      hipHostGetDevicePointer((void**)&h->out_dev, h->out, 0) != hipSuccess ||
-      hipHostMalloc((void**)&h->inl_out, E, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&h->inl_out_dev, h->inl_out, 0) != hipSuccess) {
-    set_error("rspl_frame_create: stream / pinned allocation failed");
-    rspl_frame_destroy(h);
-    return RSPL_E_DEVICE;
-  }
+  carve(h->arena, h->pinned);
   *out = h;
   return RSPL_OK;
 }
@@ -119,9 +90,7 @@ extern "C" void rspl_frame_destroy(rspl_frame* h) {
   if (!h) return;
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   h->arena.release();
-  if (h->stage) (void)hipHostFree(h->stage);
-  if (h->out) (void)hipHostFree(h->out);
-  if (h->inl_out) (void)hipHostFree(h->inl_out);
+  h->pinned.release();
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }

@@ -94,6 +94,7 @@ struct FProf {
 #define FP_ADD(k, a, b)
 #endif
 using wave::block_sum_int;
+using wave::hidx;
 
 // robust (Huber) or plain chi2 of an error, for the edge type
 __device__ __forceinline__ double cost_of(const View& V, const double* ev, bool stereo, bool robust) {
@@ -103,8 +104,6 @@ __device__ __forceinline__ double cost_of(const View& V, const double* ev, bool 
   huber(c2, stereo ? V.delta1 : V.delta0, r0, r1);
   return r0;
 }
-
-__device__ __forceinline__ int hidx(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
 
 // errors at T (stored) + robust chi2 + H / b (Huber IRLS weights), wave-reduced
 template <int NW>
@@ -167,48 +166,19 @@ __device__ __forceinline__ void linearize(const View& V, const Pose& P, int lane
   FP_ADD(4, l2, l3);
 }
 
-// (H + lambda I) x = b by Cholesky, in registers (every lane the same); false if not SPD.
-// The factor keeps 1 / L[j][j] on its diagonal.
+// (H + lambda I) x = b (wave::chol6_solve); false if not SPD
 __device__ __forceinline__ bool solve6(const double (&acc)[kNV], double lambda, double (&x)[6]) {
-  double L[6][6];
+  double L[6][6], b[6];
 #pragma unroll
   for (int i = 0; i < 6; i++)
 #pragma unroll
     for (int j = 0; j < 6; j++) L[i][j] = j >= i ? acc[hidx(i, j)] : acc[hidx(j, i)];
 #pragma unroll
-  for (int i = 0; i < 6; i++) L[i][i] += lambda;
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    double s = L[j][j];
-#pragma unroll
-    for (int k = 0; k < j; k++) s -= L[j][k] * L[j][k];
-    ok = ok && s > 0;
-    const double r = rcp64(sqrt(s));  // 1 / pivot: multiplications instead of a divide chain
-    L[j][j] = r;
-#pragma unroll
-    for (int i = j + 1; i < 6; i++) {
-      double t = L[i][j];
-#pragma unroll
-      for (int k = 0; k < j; k++) t -= L[i][k] * L[j][k];
-      L[i][j] = t * r;
-    }
-  }
-#pragma unroll
   for (int i = 0; i < 6; i++) {
-    double s = acc[21 + i];
-#pragma unroll
-    for (int k = 0; k < i; k++) s -= L[i][k] * x[k];
-    x[i] = s * L[i][i];
+    L[i][i] += lambda;
+    b[i] = acc[21 + i];
   }
-#pragma unroll
-  for (int i = 5; i >= 0; i--) {
-    double s = x[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; k++) s -= L[k][i] * x[k];
-    x[i] = s * L[i][i];
-  }
-  return ok;
+  return wave::chol6_solve(L, b, x);
 }
 
 // SparseOptimizer::optimize(iters) with OptimizationAlgorithmLevenberg on the pose vertex

@@ -19,8 +19,9 @@ struct rspl_kf {
   rspl_kf_config cfg{};
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;
+  PinnedArena pinned;
   kf::Args a{};
-  // host-mapped: the per-frame records and the frames' host arrays in ...
+  // host-mapped (pieces of `pinned`): the per-frame records and the frames' host arrays in ...
   kf::Param* params = nullptr;
   int32_t *s_tid = nullptr, *s_slot = nullptr;
   double* s_points = nullptr;
@@ -42,22 +43,13 @@ struct rspl_kf {
 
 namespace {
 
-template <typename T>
-int mapped(T** host, T** dev, size_t count) {
-  if (hipHostMalloc((void**)host, sizeof(T) * std::max<size_t>(count, 1), hipHostMallocMapped | hipHostMallocCoherent) !=
-          hipSuccess ||
-      hipHostGetDevicePointer((void**)dev, *host, 0) != hipSuccess)
-    return RSPL_E_DEVICE;
-  return RSPL_OK;
-}
-
 struct TriLayout {  // the triangulation staging for np poses, n points, m observations
   size_t poses, offsets, obs_pose, obs_xy, position, status, bytes;
   TriLayout(size_t np, size_t n, size_t m) {
     size_t o = 0;
     auto take = [&](size_t b) {
       const size_t at = o;
-      o = (o + b + 255) & ~size_t(255);
+      o = al256(o + b);
       return at;
     };
     poses = take(16 * sizeof(double) * np);
@@ -90,17 +82,26 @@ extern "C" int rspl_kf_create(const rspl_kf_config* cfg, rspl_kf** out) {
   // (a pose per observation is the most a triangulation batch can reference)
   const TriLayout lay(cfg->max_tri_observations, cfg->max_tri_points, cfg->max_tri_observations);
   kf::Args& a = h->a;
-  const bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
-                  hipEventCreateWithFlags(&h->done, hipEventDisableTiming) == hipSuccess &&
-                  mapped(&h->params, const_cast<kf::Param**>(&a.params), B) == RSPL_OK &&
-                  mapped(&h->s_tid, &h->d_tid, E) == RSPL_OK && mapped(&h->s_slot, &h->d_slot, E) == RSPL_OK &&
-                  mapped(&h->s_points, &h->d_points, 3 * E) == RSPL_OK &&
-                  mapped(&h->s_state, &h->d_state, E) == RSPL_OK && mapped(&h->out, &a.out, B) == RSPL_OK &&
-                  mapped(&h->u_right, &a.u_right, E) == RSPL_OK && mapped(&h->depth, &a.depth, E) == RSPL_OK &&
-                  mapped(&h->track_id, &a.track_id, E) == RSPL_OK &&
-                  mapped(&h->new_point, &a.new_point, E) == RSPL_OK &&
-                  mapped(&h->new_position, &a.new_position, 3 * E) == RSPL_OK &&
-                  mapped(&h->tri, &h->tri_dev, lay.bytes) == RSPL_OK;
+  auto carve = [&](auto& P) {
+    h->params = P.template take<kf::Param>(B, &a.params);
+    h->s_tid = P.template take<int32_t>(E, &h->d_tid);
+    h->s_slot = P.template take<int32_t>(E, &h->d_slot);
+    h->s_points = P.template take<double>(3 * E, &h->d_points);
+    h->s_state = P.template take<uint8_t>(E, &h->d_state);
+    h->out = P.template take<kf::Out>(B, &a.out);
+    h->u_right = P.template take<double>(E, &a.u_right);
+    h->depth = P.template take<double>(E, &a.depth);
+    h->track_id = P.template take<int32_t>(E, &a.track_id);
+    h->new_point = P.template take<uint8_t>(E, &a.new_point);
+    h->new_position = P.template take<double>(3 * E, &a.new_position);
+    h->tri = P.template take<char>(lay.bytes, &h->tri_dev);
+  };
+  Sizer psz;
+  carve(psz);
+  bool ok = h->pinned.reserve(psz.used + 256) == RSPL_OK;
+  if (ok) carve(h->pinned);
+  ok = ok && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
+       hipEventCreateWithFlags(&h->done, hipEventDisableTiming) == hipSuccess;
   if (!ok) {
     set_error("rspl_kf_create: stream / event / pinned allocation failed");
     rspl_kf_destroy(h);
@@ -115,10 +116,7 @@ extern "C" void rspl_kf_destroy(rspl_kf* h) {
   if (!h) return;
   if (h->pending && h->done) (void)hipEventSynchronize(h->done);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  void* host[] = {h->params, h->s_tid, h->s_slot, h->s_points, h->s_state, h->out, h->u_right,
-                  h->depth,  h->track_id, h->new_point, h->new_position, h->tri};
-  for (void* p : host)
-    if (p) (void)hipHostFree(p);
+  h->pinned.release();
   if (h->done) (void)hipEventDestroy(h->done);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;

@@ -11,7 +11,7 @@
 #include "kf_kernels.hpp"
 #include "kf_triangulate.hpp"
 #include "line_kernels.hpp"
-#include "track_kernels.hpp"
+#include "ransac.hpp"
 #include "wave_reduce.hpp"
 
 namespace rspl {
@@ -31,7 +31,7 @@ __device__ __forceinline__ int stereo_at(const Param& P, int i, int nl, int nr, 
   const double* l = P.feat_l + 259 * (size_t)i;
   xl = l[1];
   yl = l[2];
-  const int j = track::mutual_partner(P.idx0, P.idx1, i, nr);
+  const int j = ransac::mutual_partner(P.idx0, P.idx1, i, nr);
   if (j < 0) return 0;
   const double* r = P.feat_r + 259 * (size_t)j;
   const double xr = r[1], yr = r[2];

@@ -11,18 +11,19 @@
 
 #include "common.hpp"
 #include "pnp_kernels.hpp"
+#include "ransac.hpp"
 
 using namespace rspl;
 
 struct rspl_pnp {
   rspl_pnp_config cfg{};
   hipStream_t stream = nullptr;
+  Arena arena;
+  PinnedArena pinned;
   char* dev = nullptr;   // upload region: descs | points | keypoints | subsets
-  size_t dev_cap = 0;
-  char* stage = nullptr; // pinned, host-mapped staging, same layout
+  char* stage = nullptr; // host-mapped staging, same layout
   char* stage_dev = nullptr;  // its device pointer (the upload kernel reads it)
-  size_t stage_cap = 0;
-  pnp::Out* out = nullptr;
+  pnp::Out* out = nullptr;    // host-mapped results
   pnp::Out* out_dev = nullptr;
   uint8_t* inl = nullptr;
   uint8_t* inl_dev = nullptr;
@@ -33,8 +34,6 @@ struct rspl_pnp {
 };
 
 namespace {
-
-inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct Layout {
   size_t desc, pts, kps, sub, bytes;
@@ -50,19 +49,7 @@ struct Layout {
 // RANSACPointSetRegistrator::getSubset over cv::RNG::next
 void subsets(int count, int iters, int32_t* idx) {
   uint64_t s = (uint64_t)-1;
-  for (int h = 0; h < iters; h++) {
-    int32_t* o = idx + 5 * h;
-    for (int i = 0; i < 5; i++) {
-      int v;
-      for (;;) {
-        v = (int)(pnp::rng_next(s) % (unsigned)count);
-        bool dup = false;
-        for (int j = 0; j < i; j++) dup |= o[j] == v;
-        if (!dup) break;
-      }
-      o[i] = v;
-    }
-  }
+  for (int h = 0; h < iters; h++) ransac::draw_subset<5>(s, count, idx + 5 * h);
 }
 
 }  // namespace
@@ -73,24 +60,29 @@ extern "C" int rspl_pnp_create(const rspl_pnp_config* cfg, rspl_pnp** out) {
   RSPL_HIP(hipSetDevice(cfg->device));
   auto* h = new rspl_pnp();
   h->cfg = *cfg;
-  const Layout lay(cfg->max_batch, std::max(cfg->max_points, 1), (size_t)cfg->max_batch * pnp::kMaxIters);
-  h->dev_cap = h->stage_cap = lay.bytes;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void**)&h->dev, lay.bytes) != hipSuccess ||
-      hipHostMalloc((void**)&h->stage, lay.bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&h->stage_dev, h->stage, 0) != hipSuccess ||
-      hipHostMalloc((void**)&h->out, sizeof(pnp::Out) * cfg->max_batch, hipHostMallocMapped | hipHostMallocCoherent) !=
-          hipSuccess ||
-      hipHostGetDevicePointer((void**)&h->out_dev, h->out, 0) != hipSuccess ||
-      hipHostMalloc((void**)&h->inl, std::max(cfg->max_points, 1), hipHostMallocMapped | hipHostMallocCoherent) !=
-          hipSuccess ||
-      hipHostGetDevicePointer((void**)&h->inl_dev, h->inl, 0) != hipSuccess ||
-      hipMalloc((void**)&h->hyp, sizeof(double) * 12 * pnp::kMaxIters * cfg->max_batch) != hipSuccess ||
-      hipMalloc((void**)&h->hcnt, sizeof(int) * pnp::kMaxIters * cfg->max_batch) != hipSuccess) {
-    set_error("rspl_pnp_create: allocation failed");
-    rspl_pnp_destroy(h);
-    return RSPL_E_DEVICE;
+  const size_t B = cfg->max_batch, P = std::max(cfg->max_points, 1);
+  const Layout lay(cfg->max_batch, P, B * pnp::kMaxIters);
+  auto carve = [&](auto& A, auto& M) {
+    h->dev = A.template take<char>(lay.bytes);
+    h->hyp = A.template take<double>(12 * pnp::kMaxIters * B);
+    h->hcnt = A.template take<int>(pnp::kMaxIters * B);
+    h->stage = M.template take<char>(lay.bytes, &h->stage_dev);
+    h->out = M.template take<pnp::Out>(B, &h->out_dev);
+    h->inl = M.template take<uint8_t>(P, &h->inl_dev);
+  };
+  Sizer sz, psz;
+  carve(sz, psz);
+  int rc = h->arena.reserve(sz.used + 256);
+  if (!rc) rc = h->pinned.reserve(psz.used + 256);
+  if (!rc && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+    set_error("rspl_pnp_create: stream creation failed");
+    rc = RSPL_E_DEVICE;
   }
+  if (rc) {
+    rspl_pnp_destroy(h);
+    return rc;
+  }
+  carve(h->arena, h->pinned);
   *out = h;
   return RSPL_OK;
 }
@@ -98,12 +90,8 @@ extern "C" int rspl_pnp_create(const rspl_pnp_config* cfg, rspl_pnp** out) {
 extern "C" void rspl_pnp_destroy(rspl_pnp* h) {
   if (!h) return;
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->dev) (void)hipFree(h->dev);
-  if (h->stage) (void)hipHostFree(h->stage);
-  if (h->out) (void)hipHostFree(h->out);
-  if (h->inl) (void)hipHostFree(h->inl);
-  if (h->hyp) (void)hipFree(h->hyp);
-  if (h->hcnt) (void)hipFree(h->hcnt);
+  h->arena.release();
+  h->pinned.release();
   if (h->prof) (void)hipFree(h->prof);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;

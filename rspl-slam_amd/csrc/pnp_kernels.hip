@@ -21,6 +21,7 @@
 #include <cstdint>
 
 #include "pnp_kernels.hpp"
+#include "ransac.hpp"
 #include "wave_reduce.hpp"
 
 // No FMA contraction in this file: EPnP on 5 points has a degenerate (>= 2-dimensional) null
@@ -625,18 +626,6 @@ __device__ int epnp_wave(const double* K4, const double (&pw)[3 * kN], const dou
   return 0;
 }
 
-/* RANSACUpdateNumIters */
-__device__ int update_iters(double p, double ep, int model_points, int max_iters) {
-  p = fmin(fmax(p, 0.), 1.);
-  ep = fmin(fmax(ep, 0.), 1.);
-  double num = fmax(1. - p, DBL_MIN);
-  double denom = 1. - pow(1. - ep, model_points);
-  if (denom < DBL_MIN) return 0;
-  num = log(num);
-  denom = log(denom);
-  return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)rint(num / denom);
-}
-
 __device__ double reproj2(const double* K4, const double R[9], const double t[3], const double* p, const double* uv) {
   const double Xc = dot3(R, p) + t[0], Yc = dot3(R + 3, p) + t[1], Zc = dot3(R + 6, p) + t[2];
   const double iz = 1.0 / Zc;
@@ -677,56 +666,24 @@ __device__ void refine(const double* K4, int n, const double* pw, const double* 
         }
       for (int a = 0; a < 6; a++) {
         acc[21 + a] += -(J[0][a] * e0 + J[1][a] * e1);
-        for (int b = a; b < 6; b++) acc[a * 6 - a * (a - 1) / 2 + (b - a)] += J[0][a] * J[0][b] + J[1][a] * J[1][b];
+        for (int b = a; b < 6; b++) acc[wave::hidx(a, b)] += J[0][a] * J[0][b] + J[1][a] * J[1][b];
       }
     }
     wave::block_allreduce28<NW>(acc, lane);
     const double cost = acc[27];
-    auto H = [&](int a, int b) { return a <= b ? acc[a * 6 - a * (a - 1) / 2 + (b - a)] : acc[b * 6 - b * (b - 1) / 2 + (a - b)]; };
+    auto H = [&](int a, int b) { return a <= b ? acc[wave::hidx(a, b)] : acc[wave::hidx(b, a)]; };
     bool accepted = false;
     for (int trial = 0; trial < 10 && !accepted; trial++) {
-      double A[6][6], x[6];
+      double A[6][6], g[6], x[6];
       for (int i = 0; i < 6; i++)
         for (int j = 0; j < 6; j++) A[i][j] = H(i, j);
       for (int i = 0; i < 6; i++) A[i][i] += lambda * fmax(H(i, i), 1e-12);
-      for (int i = 0; i < 6; i++) x[i] = acc[21 + i];
-      // Cholesky with the pivots' reciprocals on the diagonal: one v_rcp_f64 + Newton per
-      // column instead of a divide per entry (the refined optimum agrees with the oracle's
-      // divides to rounding; the tests hold it to 1e-9)
-      bool ok = true;
-#pragma unroll
-      for (int j = 0; j < 6; j++) {
-        double s = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) s -= A[j][k] * A[j][k];
-        ok = ok && s > 0;
-        const double r = wave::rcp64(sqrt(s));
-        A[j][j] = r;
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-          double v = A[i][j];
-#pragma unroll
-          for (int k = 0; k < j; k++) v -= A[i][k] * A[j][k];
-          A[i][j] = v * r;
-        }
-      }
-      if (!ok) {
+      for (int i = 0; i < 6; i++) g[i] = acc[21 + i];
+      // (the factor's reciprocal pivots: the refined optimum agrees with the oracle's divides to rounding; the
+      // tests hold it to 1e-9)
+      if (!wave::chol6_solve(A, g, x)) {
         lambda *= 10;
         continue;
-      }
-#pragma unroll
-      for (int i = 0; i < 6; i++) {
-        double s = x[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) s -= A[i][k] * x[k];
-        x[i] = s * A[i][i];
-      }
-#pragma unroll
-      for (int i = 5; i >= 0; i--) {
-        double s = x[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) s -= A[k][i] * x[k];
-        x[i] = s * A[i][i];
       }
       const double* w = x;
       const double th = sqrt(dot3(w, w));
@@ -768,12 +725,6 @@ __device__ void refine(const double* K4, int n, const double* pw, const double* 
     }
     if (!accepted) return;
   }
-}
-
-// squared reprojection error of world point p (pixels), pinhole K4 = (fx, fy, cx, cy)
-__device__ __forceinline__ double proj_err2(const double* K4, const double* R, const double* t, const double* p,
-                                            const double* uv) {
-  return reproj2(K4, R, t, p, uv);
 }
 
 // stage 1: wave w of workgroup (bx, frame) solves hypothesis 4 bx + w and counts its inliers
@@ -834,7 +785,7 @@ __global__ __launch_bounds__(64 * kFinalWaves) void pnp_final_kernel(Args a) {
       if (c > (best_cnt > 4 ? best_cnt : 4)) {
         best = h;
         best_cnt = c;
-        niters = update_iters(D.confidence, (double)(n - c) / n, 5, niters);
+        niters = ransac::update_num_iters(D.confidence, (double)(n - c) / n, 5, niters);
       }
     }
     used = h;

@@ -36,12 +36,6 @@ struct Args {
                              // [0, 8) and of its acceptance / refinement [8, 12)
 };
 
-// cv::RNG::next (multiply-with-carry), the generator RANSACPointSetRegistrator::run seeds with (uint64)-1
-inline unsigned rng_next(uint64_t& s) {
-  s = (uint64_t)(unsigned)s * 4164903690u + (unsigned)(s >> 32);
-  return (unsigned)s;
-}
-
 // max_iters: the largest RANSAC iteration count of the batch (hypothesis grid width)
 hipError_t solve(const Args& a, int batch, int max_iters, hipStream_t s);
 

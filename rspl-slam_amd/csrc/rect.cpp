@@ -25,6 +25,7 @@ struct rspl_rect {
   std::vector<float> map_x[2], map_y[2];
   std::vector<uint32_t> h_table;  // staging of one camera's table
   Arena arena;
+  PinnedArena pinned;
   uint32_t* table = nullptr;  // device [2][H][tpitch]
   uint8_t *raw = nullptr, *out = nullptr;  // device [2][H][W] each: rspl_rect_pair's images
   uint8_t *h_raw = nullptr, *h_raw_dev = nullptr;  // host-mapped pinned slot and its device address
@@ -232,8 +233,7 @@ extern "C" int rspl_rect_create(const rspl_rect_config* cfg, rspl_rect** out) {
     h->raw = h->arena.take<uint8_t>(2 * px);
     h->out = h->arena.take<uint8_t>(2 * px);
     ok = h->table && h->raw && h->out &&
-         hipHostMalloc((void**)&h->h_raw, 2 * px, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
-         hipHostGetDevicePointer((void**)&h->h_raw_dev, h->h_raw, 0) == hipSuccess &&
+         h->pinned.reserve(2 * px) == RSPL_OK && (h->h_raw = h->pinned.take<uint8_t>(2 * px, &h->h_raw_dev)) &&
          hipHostMalloc((void**)&h->h_out, 2 * px) == hipSuccess && upload_table(h, 0) == RSPL_OK &&
          upload_table(h, 1) == RSPL_OK;
   }
@@ -249,7 +249,7 @@ extern "C" int rspl_rect_create(const rspl_rect_config* cfg, rspl_rect** out) {
 extern "C" void rspl_rect_destroy(rspl_rect* h) {
   if (!h) return;
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->h_raw) (void)hipHostFree(h->h_raw);
+  h->pinned.release();
   if (h->h_out) (void)hipHostFree(h->h_out);
   h->arena.release();
   if (h->stream) (void)hipStreamDestroy(h->stream);

@@ -122,6 +122,7 @@ extern "C" int rspl_sp_create(const rspl_sp_config* cfg, const char* weights_pat
                      cfg->precision == RSPL_PREC_FP16X3,
                  "precision must be RSPL_PREC_FP32, RSPL_PREC_FP16 or RSPL_PREC_FP16X3");
   RSPL_CHECK_ARG(cfg->remove_borders >= 0, "remove_borders must be >= 0");
+  RSPL_CHECK_ARG(cfg->max_keypoints <= kCandCap, "max_keypoints must be <= %d", kCandCap);
   *out = nullptr;
   std::vector<Tensor> ts;
   int rc = load_blob(weights_path, ts);
@@ -131,7 +132,6 @@ extern "C" int rspl_sp_create(const rspl_sp_config* cfg, const char* weights_pat
   s->cfg = *cfg;
   if (s->cfg.max_batch < 1) s->cfg.max_batch = 1;
   const int B = s->cfg.max_batch, H = cfg->max_height, W = cfg->max_width;
-  RSPL_CHECK_ARG(cfg->max_keypoints <= kCandCap, "max_keypoints must be <= %d", kCandCap);
   s->feat_cap = cfg->max_keypoints > 0 ? cfg->max_keypoints : kCandCap;
   // one slot per pixel: the candidate buffer cannot overflow whatever survives simple_nms
   // (flat plateaus keep every tied pixel), so no device path ever truncates it

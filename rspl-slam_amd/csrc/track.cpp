@@ -13,6 +13,7 @@
 
 #include "common.hpp"
 #include "line_kernels.hpp"
+#include "ransac.hpp"
 #include "track_kernels.hpp"
 #include "track_line_kernels.hpp"
 
@@ -23,6 +24,7 @@ struct rspl_track {
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;
   Arena arena;
+  PinnedArena pinned;
   track::Args ta{};
   pnp::Args pa{};
   frame::Args fa{};
@@ -34,18 +36,19 @@ struct rspl_track {
   size_t kf_stage_slot = 0;
   std::vector<hipEvent_t> kf_ev;
   std::vector<int> n0;  // -1: the slot was never set
-  // host-mapped: the per-frame parameters in, the results out
+  // host-mapped (pieces of `pinned`): the per-frame parameters in, the results out
   track::Param* params = nullptr;
   track::Out* out = nullptr;
   int32_t *o_match_kf = nullptr, *o_track_id = nullptr;
   uint8_t* o_kept = nullptr;
   bool pending = false;
   int batch = 0;  // frames of the last enqueue
-  // the line side (rspl_track_enable_lines): its own arena, the slots' id staging, host-mapped parameters / results
+  // the line side (rspl_track_enable_lines): its own arenas, the slots' id staging, host-mapped parameters / results
   bool lines_on = false;
   bool ext = false;  // the last enqueue was rspl_track_enqueue_ext
   rspl_track_lines_config lcfg{};
   Arena larena;
+  PinnedArena lpinned;
   track::LineArgs la{};
   std::vector<int> kf_nl;  // lines of each slot, 0 until set
   char* kfl_stage = nullptr;
@@ -58,70 +61,15 @@ struct rspl_track {
 
 namespace {
 
-// the raw draws of RANSAC's generator (csrc/pnp.cpp subsets()), which do not depend on the correspondence count
-std::vector<uint32_t> raw_draws(int n) {
-  std::vector<uint32_t> d(n);
-  uint64_t s = (uint64_t)-1;
-  for (int k = 0; k < n; k++) d[k] = pnp::rng_next(s);
-  return d;
-}
-
-// The draws kMaxIters subsets consume for `count` correspondences (getSubset: a duplicate draws again), or
-// -1 when the table ends first.
-int draws_needed(const std::vector<uint32_t>& d, int count) {
-  size_t pos = 0;
-  for (int h = 0; h < pnp::kMaxIters; h++) {
-    int o[5];
-    for (int i = 0; i < 5; i++) {
-      for (;;) {
-        if (pos >= d.size()) return -1;
-        const int v = (int)(d[pos++] % (unsigned)count);
-        bool dup = false;
-        for (int j = 0; j < i; j++) dup |= o[j] == v;
-        if (!dup) {
-          o[i] = v;
-          break;
-        }
-      }
-    }
-  }
-  return (int)pos;
-}
-
-struct Count {  // the size-only pass of the arena carving
-  size_t used = 0;
-  template <typename T>
-  T* take(size_t count) {
-    used = ((used + 255) & ~size_t(255)) + count * sizeof(T);
-    return nullptr;
-  }
-};
-
-template <typename T>
-int mapped(T** host, T** dev, size_t count) {
-  if (hipHostMalloc((void**)host, sizeof(T) * std::max<size_t>(count, 1), hipHostMallocMapped | hipHostMallocCoherent) !=
-          hipSuccess ||
-      hipHostGetDevicePointer((void**)dev, *host, 0) != hipSuccess)
-    return RSPL_E_DEVICE;
-  return RSPL_OK;
-}
-
 // what rspl_track_enable_lines allocated (all of it or, after a failure there, a part)
 void release_lines(rspl_track* h) {
   for (hipEvent_t e : h->kfl_ev)
     if (e) (void)hipEventDestroy(e);
   h->kfl_ev.clear();
   h->larena.release();
-  auto drop = [](auto*& p) {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-  };
-  drop(h->kfl_stage);
-  drop(h->lparams);
-  drop(h->lout);
-  drop(h->o_lmatch);
-  drop(h->o_ltid);
-  drop(h->o_lslot);
+  h->lpinned.release();
+  if (h->kfl_stage) (void)hipHostFree(h->kfl_stage);
+  h->kfl_stage = nullptr;
 }
 
 }  // namespace
@@ -137,10 +85,10 @@ extern "C" int rspl_track_create(const rspl_track_config* cfg, rspl_track** out)
   // kMaxIters subsets consume are computed here for EVERY count an enqueue can meet (8 .. max_keypoints)
   // and the maximum taken (count 8 rejects most: 4 of 8 values are duplicates for a subset's last index).
   const int B = cfg->max_batch, K = cfg->max_keypoints;
-  std::vector<uint32_t> draws = raw_draws(track::kDrawCap);
+  std::vector<uint32_t> draws = ransac::raw_draws(track::kDrawCap);
   int nd = 0;
   for (int c = 8; c <= K; c++) {
-    const int need = draws_needed(draws, c);
+    const int need = ransac::draws_needed<5>(draws, c, pnp::kMaxIters);
     RSPL_CHECK_ARG(need >= 0, "rspl_track_create: %d correspondences need more than %d RNG draws", c, track::kDrawCap);
     nd = std::max(nd, need);
   }
@@ -157,7 +105,12 @@ extern "C" int rspl_track_create(const rspl_track_config* cfg, rspl_track** out)
   uint32_t* d_draws = nullptr;
   pnp::Out* pnp_out = nullptr;
   frame::Out* frame_out = nullptr;
-  auto carve = [&](auto& A) {
+  auto carve = [&](auto& A, auto& P) {
+    h->params = P.template take<track::Param>(B, &t.host_params);
+    h->out = P.template take<track::Out>(B, &t.out);
+    h->o_match_kf = P.template take<int32_t>(E, &t.o_match_kf);
+    h->o_track_id = P.template take<int32_t>(E, &t.o_track_id);
+    h->o_kept = P.template take<uint8_t>(E, &t.o_kept);
     d_draws = A.template take<uint32_t>(draws.size());
     h->kf_points = A.template take<double>(3 * E);
     h->kf_tid = A.template take<int32_t>(E);
@@ -187,21 +140,19 @@ extern "C" int rspl_track_create(const rspl_track_config* cfg, rspl_track** out)
     f.inl_out = A.template take<uint8_t>(E);
     frame_out = A.template take<frame::Out>(B);
   };
-  Count sz;
-  carve(sz);
+  Sizer sz, psz;
+  carve(sz, psz);
   int rc = h->arena.reserve(sz.used + 256);
+  if (!rc) rc = h->pinned.reserve(psz.used + 256);
   if (rc) {
-    delete h;
+    rspl_track_destroy(h);
     return rc;
   }
-  carve(h->arena);
-  h->kf_stage_slot = ((size_t)K * (3 * sizeof(double) + sizeof(int32_t) + 1) + 255) & ~size_t(255);
+  carve(h->arena, h->pinned);
+  h->kf_stage_slot = al256((size_t)K * (3 * sizeof(double) + sizeof(int32_t) + 1));
   bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&h->done, hipEventDisableTiming) == hipSuccess &&
-            hipHostMalloc((void**)&h->kf_stage, h->kf_stage_slot * B, hipHostMallocDefault) == hipSuccess &&
-            mapped(&h->params, const_cast<track::Param**>(&t.host_params), B) == RSPL_OK &&
-            mapped(&h->out, &t.out, B) == RSPL_OK && mapped(&h->o_match_kf, &t.o_match_kf, E) == RSPL_OK &&
-            mapped(&h->o_track_id, &t.o_track_id, E) == RSPL_OK && mapped(&h->o_kept, &t.o_kept, E) == RSPL_OK;
+            hipHostMalloc((void**)&h->kf_stage, h->kf_stage_slot * B, hipHostMallocDefault) == hipSuccess;
   for (int s = 0; ok && s < B; s++) ok = hipEventCreateWithFlags(&h->kf_ev[s], hipEventDisableTiming) == hipSuccess;
   // (the scratch is zeroed once so that a debug read-back of slots no kernel wrote is defined)
   ok = ok && hipMemset(h->arena.base, 0, h->arena.used) == hipSuccess &&
@@ -243,13 +194,9 @@ extern "C" void rspl_track_destroy(rspl_track* h) {
     if (e) (void)hipEventSynchronize(e);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   h->arena.release();
+  h->pinned.release();
   release_lines(h);
   if (h->kf_stage) (void)hipHostFree(h->kf_stage);
-  if (h->params) (void)hipHostFree(h->params);
-  if (h->out) (void)hipHostFree(h->out);
-  if (h->o_match_kf) (void)hipHostFree(h->o_match_kf);
-  if (h->o_track_id) (void)hipHostFree(h->o_track_id);
-  if (h->o_kept) (void)hipHostFree(h->o_kept);
   if (h->done) (void)hipEventDestroy(h->done);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -418,7 +365,12 @@ extern "C" int rspl_track_enable_lines(rspl_track* h, const rspl_track_lines_con
   RSPL_HIP(hipSetDevice(h->cfg.device));
   const size_t S = h->cfg.max_batch, K = h->cfg.max_keypoints, ML = cfg->max_lines, cap = cfg->max_pairs;
   track::LineArgs& g = h->la;
-  auto carve = [&](auto& A) {
+  auto carve = [&](auto& A, auto& P) {
+    h->lparams = P.template take<track::LineParam>(S, &g.lparams);
+    h->lout = P.template take<track::LineOut>(S, &g.out);
+    h->o_lmatch = P.template take<int32_t>(S * ML, &g.o_line_match);
+    h->o_ltid = P.template take<int32_t>(S * ML, &g.o_line_tid);
+    h->o_lslot = P.template take<int32_t>(S * ML, &g.o_line_slot);
     g.kf_off = A.template take<int>(S * (ML + 1));
     g.kf_idx = A.template take<int>(S * cap);
     g.kf_dist = A.template take<double>(S * cap);
@@ -436,18 +388,19 @@ extern "C" int rspl_track_enable_lines(rspl_track* h, const rspl_track_lines_con
     g.line_tid = A.template take<int32_t>(S * ML);
     g.line_slot = A.template take<int32_t>(S * ML);
   };
-  Count sz;
-  carve(sz);
+  Sizer sz, psz;
+  carve(sz, psz);
   int rc = h->larena.reserve(sz.used + 256);
-  if (rc) return rc;
-  carve(h->larena);
+  if (!rc) rc = h->lpinned.reserve(psz.used + 256);
+  if (rc) {
+    release_lines(h);
+    return rc;
+  }
+  carve(h->larena, h->lpinned);
   h->kf_nl.assign(S, 0);
   h->kfl_ev.assign(S, nullptr);
-  h->kfl_stage_slot = (2 * sizeof(int32_t) * ML + 255) & ~size_t(255);
-  bool ok = hipHostMalloc((void**)&h->kfl_stage, h->kfl_stage_slot * S, hipHostMallocDefault) == hipSuccess &&
-            mapped(&h->lparams, const_cast<track::LineParam**>(&g.lparams), S) == RSPL_OK &&
-            mapped(&h->lout, &g.out, S) == RSPL_OK && mapped(&h->o_lmatch, &g.o_line_match, S * ML) == RSPL_OK &&
-            mapped(&h->o_ltid, &g.o_line_tid, S * ML) == RSPL_OK && mapped(&h->o_lslot, &g.o_line_slot, S * ML) == RSPL_OK;
+  h->kfl_stage_slot = al256(2 * sizeof(int32_t) * ML);
+  bool ok = hipHostMalloc((void**)&h->kfl_stage, h->kfl_stage_slot * S, hipHostMallocDefault) == hipSuccess;
   for (size_t s = 0; ok && s < S; s++) ok = hipEventCreateWithFlags(&h->kfl_ev[s], hipEventDisableTiming) == hipSuccess;
   // (zeroed once: a slot whose lines were never set has status 0, and a debug read-back is defined)
   ok = ok && hipMemset(h->larena.base, 0, h->larena.used) == hipSuccess;

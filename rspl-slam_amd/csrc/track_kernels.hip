@@ -8,6 +8,7 @@
 // Ordering: every compaction is a ballot + lane-count prefix inside a wave, wave totals through LDS and a
 // running base over chunks of 256 keypoints -- no atomics, so slot order is ascending keypoint index, the
 // reference's loop order, by construction.
+#include "ransac.hpp"
 #include "se3_device.hpp"
 #include "track_kernels.hpp"
 #include "wave_reduce.hpp"
@@ -18,30 +19,9 @@ namespace {
 
 constexpr int T = 256, NW = 4;
 
+using ransac::mutual_partner;
+using ransac::subset_at;
 using wave::lanes_below;
-
-// RANSACPointSetRegistrator::getSubset started at draw k of the (already reduced % count) stream dv[0, nd):
-// 5 distinct values, a duplicate draws again.  Returns the draws consumed, 0 when the table ends first.
-__device__ __forceinline__ int subset_at(const int* dv, int nd, int k, int (&o)[5]) {
-  int pos = k;
-#pragma unroll
-  for (int i = 0; i < 5; i++) o[i] = -1;
-#pragma unroll
-  for (int i = 0; i < 5; i++) {
-    for (;;) {
-      if (pos >= nd) return 0;
-      const int v = dv[pos++];
-      bool dup = false;
-#pragma unroll
-      for (int j = 0; j < 5; j++) dup |= j < i && o[j] == v;
-      if (!dup) {
-        o[i] = v;
-        break;
-      }
-    }
-  }
-  return pos - k;
-}
 
 // SE3Quat::inverse as frame.cpp's host code spells it
 __device__ __forceinline__ ba::SE3 se3_inverse(const ba::SE3& X) {

@@ -11,13 +11,6 @@ namespace track {
 
 constexpr int kDrawCap = 2048;  // raw RNG draws the gather kernel can index (its LDS run-length table)
 
-// The mutual check of point_matching.cc:24-31 from one side: keypoint i's partner on the other side
-// (n_other keypoints), or -1.  fwd = this side's indices (i -> partner), back = the other side's.
-__host__ __device__ __forceinline__ int mutual_partner(const int32_t* fwd, const int32_t* back, int i, int n_other) {
-  const int j = fwd[i];
-  return (j >= 0 && j < n_other && back[j] == i) ? j : -1;
-}
-
 struct Param {  // one frame of the batch, written by the host into host-mapped memory
   const double* feat;      // [cap][259]
   const int32_t* n1;

@@ -1,7 +1,7 @@
 // Wavefront (wave64) reductions shared by the single-wave fp64 solvers (frame_kernels.hip,
 // pnp_kernels.hip): DPP all-reduce sums that leave the bitwise-same value in every lane, a
-// reduce-scatter all-reduce of the 28-value 6x6 normal equations, and a full-precision
-// reciprocal without the divide sequence.
+// reduce-scatter all-reduce of the 28-value 6x6 normal equations, a full-precision
+// reciprocal without the divide sequence, and the 6x6 Cholesky solve both solvers' LM steps take.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -122,6 +122,49 @@ __device__ __forceinline__ double rcp64(double d) {
   double r = __builtin_amdgcn_rcp(d);
   r = fma(r, fma(-d, r, 1.0), r);
   return fma(r, fma(-d, r, 1.0), r);
+}
+
+// index of H(i, j), i <= j, in the packed upper triangle (the first 21 of the kNV values)
+__device__ __forceinline__ int hidx(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
+
+// A x = b by Cholesky, in registers (every lane the same); false if A is not SPD (x is then meaningless).
+// A is overwritten by the factor, which keeps 1 / L[j][j] on its diagonal: one rcp64 per column and
+// multiplications instead of a divide chain.  An fp contract pragma is lexical: this body is compiled under the
+// setting at the point this header is included (both users include it under the default, fast -- what
+// FrameOptimization and PnP's refinement each had around their own copy), not under the caller's.
+__device__ __forceinline__ bool chol6_solve(double (&A)[6][6], const double (&b)[6], double (&x)[6]) {
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    double s = A[j][j];
+#pragma unroll
+    for (int k = 0; k < j; k++) s -= A[j][k] * A[j][k];
+    ok = ok && s > 0;
+    const double r = rcp64(sqrt(s));
+    A[j][j] = r;
+#pragma unroll
+    for (int i = j + 1; i < 6; i++) {
+      double t = A[i][j];
+#pragma unroll
+      for (int k = 0; k < j; k++) t -= A[i][k] * A[j][k];
+      A[i][j] = t * r;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    double s = b[i];
+#pragma unroll
+    for (int k = 0; k < i; k++) s -= A[i][k] * x[k];
+    x[i] = s * A[i][i];
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; i--) {
+    double s = x[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; k++) s -= A[k][i] * x[k];
+    x[i] = s * A[i][i];
+  }
+  return ok;
 }
 
 // A workgroup of NW waves (FrameOptimization's frame, PnP's refinement): a wave-reduced value (equal on every

@@ -203,3 +203,35 @@ def classify_e2e_disagreements(Fa, Fb, Za, Zb, threshold, score_tol, z_tol, k=40
             if cls == "unexplained":
                 bad.append((side, m))
     return counts, bad
+
+
+def cycle_handle(make, run, times=20):
+    """Create and destroy a handle `times` times -- the wrappers destroy theirs when the last reference goes --
+    running `run` on the first; then `run` once more on a fresh handle.  Returns (first result, last result):
+    every release path of the handle has run `times` times in between."""
+    first = None
+    for k in range(times):
+        h = make()
+        if k == 0:
+            first = run(h)
+        del h
+    return first, run(make())
+
+
+def assert_same(a, b):
+    """Two results of the same call, bit for bit (dicts, sequences, arrays, result records, scalars)."""
+    assert type(a) is type(b)
+    if isinstance(a, dict):
+        assert a.keys() == b.keys()
+        for k in a:
+            assert_same(a[k], b[k])
+    elif isinstance(a, (list, tuple)):
+        assert len(a) == len(b)
+        for x, y in zip(a, b):
+            assert_same(x, y)
+    elif isinstance(a, np.ndarray):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    elif hasattr(a, "__dict__"):
+        assert_same(vars(a), vars(b))
+    else:
+        assert a == b

@@ -267,3 +267,20 @@ def test_filtered_indices_feed_the_tracker(fm):
                      last_Twc=p["last_Twc"])])
     (t,) = tr.fetch()
     assert t["n_matches"] == r["n_inliers"]
+
+
+def test_create_destroy_cycle():
+    """20 handles of the smallest capacities created and destroyed (device arena, pinned arena, stream, event),
+    then one more: its host-fed solve and its device-resident chain equal the first handle's bit for bit."""
+    from helpers import assert_same, cycle_handle
+    p0, p1, _, _ = FC.checked_scene(8, 0.0, 0.0, 2)
+    c = _chain_case(8, 0.0, seed=8)
+
+    def run(h):
+        solved = h.solve([(p0, p1)])
+        res, outs, _ = _enqueue(h, [c])
+        return solved, res, outs
+
+    first, last = cycle_handle(lambda: pkg.FundamentalRansac(max_batch=1, max_matches=8), run)
+    assert first[0][0]["n_inliers"] > 0 and first[1][0]["n_inliers"] > 0
+    assert_same(first, last)

@@ -94,3 +94,15 @@ def test_frame_alone_and_in_a_large_batch(fba):
     alone = fba.run(probs[:1])[0]
     batch = fba.run(probs)[0]
     _compare(alone, batch)
+
+
+def test_create_destroy_cycle():
+    """20 handles of the smallest capacities created and destroyed (device arena, pinned arena, stream), then
+    one more: its result equals the first handle's bit for bit."""
+    import rspl_loader
+    from helpers import assert_same, cycle_handle
+    pkg = rspl_loader.load()
+    prob, gt = SY.frame_problem(n_points=8, outlier_frac=0.0, seed=0)
+    first, last = cycle_handle(lambda: pkg.FrameBA(max_batch=1, max_edges=8, max_points=8), lambda h: h.run([prob]))
+    assert first[0].n_inliers > 0
+    assert_same(first, last)

@@ -257,3 +257,21 @@ def test_end_to_end_raw_sequence(kf):
     assert sum(r["n_lines_triangulated"] for r in reports) > 0
     assert all(r["optimization"] is not None for r in reports[1:]) and reports[0]["optimization"] is None
     assert next_tid == stages[-1]["next_track_id"] == len(seq["point_ids"])
+
+
+def test_create_destroy_cycle():
+    """20 handles of the smallest capacities created and destroyed (pinned arena, stream, event), then one more:
+    its stereo stage and its triangulation equal the first handle's bit for bit."""
+    from helpers import assert_same, cycle_handle
+    p = SY.keyframe_problem(n_left=8, n_right=8, n_common=6, seed=1)
+    poses, off, op, xy, _ = tri_cases()
+    off = off[:9]  # 8 points
+    m = int(off[-1])
+
+    def run(h):
+        return _run(h, [p]), h.triangulate(poses, CAM, off, op[:m], xy[:m])
+
+    first, last = cycle_handle(lambda: pkg.KeyframeBuilder(max_batch=1, max_keypoints=8, max_tri_points=8,
+                                                           max_tri_observations=max(m, len(poses))), run)
+    assert first[0][0]["n_matches"] > 0
+    assert_same(first, last)

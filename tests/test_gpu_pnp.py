@@ -97,3 +97,15 @@ def test_pnp_matches_independent_restatement(pnp, seed, n, outl, sig):
     assert n_g == rn
     np.testing.assert_array_equal(inl, rinl)
     assert np.abs(R - rR).max() < 1e-7 and np.abs(t - rt).max() < 1e-6
+
+
+def test_create_destroy_cycle():
+    """20 handles of the smallest capacities created and destroyed (device arena, pinned arena, stream), then
+    one more: its solve equals the first handle's bit for bit."""
+    import rspl_loader
+    from helpers import assert_same, cycle_handle
+    pkg = rspl_loader.load()
+    K, X, kp, gt = SY.pnp_problem(n_points=8, outlier_frac=0.0, pixel_sigma=0.5, seed=4)
+    first, last = cycle_handle(lambda: pkg.PnP(max_batch=1, max_points=8), lambda h: h.solve([(K, X, kp)]))
+    assert first[0][0] > 0
+    assert_same(first, last)

@@ -227,3 +227,13 @@ def test_chain_into_superpoint_on_one_stream(weight_blobs, golden):
     ref_feat, ref_cnt = superpoint(d_ref, s)
     assert cnt.tobytes() == ref_cnt.tobytes() and cnt.min() > 0, (cnt, ref_cnt)
     assert feat.tobytes() == ref_feat.tobytes()
+
+
+def test_create_destroy_cycle():
+    """20 rectifiers of a small size created and destroyed (device arena, pinned slot, stream), then one more:
+    its host pair equals the first handle's bit for bit."""
+    from helpers import assert_same, cycle_handle
+    W, H = 16, 8
+    left, right = _images(np.random.default_rng(3), 2, H, W)
+    first, last = cycle_handle(lambda: _rectifier(W, H, max_batch=1)[0], lambda r: r.pair(left, right))
+    assert_same(first, last)

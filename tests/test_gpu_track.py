@@ -273,3 +273,13 @@ def test_re_enqueue_leaks_no_state(tr):
     (rf,), _ = _run(fresh, [small])
     for k in ("pose_q", "pose_p", "track_id", "kept", "match_kf", "chi2"):
         np.testing.assert_array_equal(rs[k], rf[k], err_msg=k)
+
+
+def test_create_destroy_cycle():
+    """20 handles of the smallest capacities created and destroyed (device arena, pinned arena, staging, stream,
+    events), then one more: its enqueue + fetch and debug stages equal the first handle's bit for bit."""
+    from helpers import assert_same, cycle_handle
+    p = _problem(8)
+    first, last = cycle_handle(lambda: pkg.Tracker(max_batch=1, max_keypoints=8), lambda t: _run(t, [p]))
+    assert len(first[1][0]["subsets"]) == 100  # 8 correspondences: PnP ran
+    assert_same(first, last)

@@ -279,3 +279,20 @@ def test_argument_checks(tr, plain):
         big.enable_lines(max_lines=ML, max_pairs=CAP)             # more keypoints than a line workgroup holds
     (r,), (d,) = _run(tr, [c])                                    # the refusals left the handle usable
     _check_lines(r, d, _ref(c))
+
+
+def test_create_destroy_cycle():
+    """20 handles of the smallest capacities with the line side enabled, created and destroyed (both device
+    arenas, both pinned arenas, both stagings, stream, events), then one more: its enqueue_ext + fetch and debug
+    read-back equal the first handle's bit for bit."""
+    from helpers import assert_same, cycle_handle
+    c = TC.line_case(4, 8)
+
+    def make():
+        t = pkg.Tracker(max_batch=1, max_keypoints=8)
+        t.enable_lines(max_lines=8, max_pairs=64)
+        return t
+
+    first, last = cycle_handle(make, lambda t: _run(t, [c]))
+    assert first[0][0]["n_lines"] == 4
+    assert_same(first, last)
