@@ -423,6 +423,23 @@ int rspl_ba_debug_chunk_plan(int n_landmarks, int n_poses, int max_landmarks, in
                              rspl_ba_chunk_plan* out);
 int rspl_ba_debug_chunk_geometry(int n_landmarks, int n_poses, int max_landmarks, int max_poses, int32_t* chunks,
                                  int32_t* order);
+/* Test hook (host only, no device): the segment offsets of the Schur chunks' edge-pair lists as the staging of
+ * rspl_ba_local counts them for `problem` in a handle created for max_landmarks / max_poses -- pp_off[c] for
+ * c <= *n_chunks (cap: ints of room): chunk c (rspl_ba_debug_chunk_geometry) owns pairs [pp_off[c], pp_off[c+1]),
+ * one per (edge on the pair's first pose, edge on its second pose) of each landmark of its range. */
+int rspl_ba_debug_pair_offsets(const rspl_ba_problem* problem, int max_landmarks, int max_poses, int32_t* pp_off,
+                               int cap, int* n_chunks);
+/* Test hooks (device) on the last completed unsharded rspl_ba_local call of the handle.
+ * rspl_ba_debug_pairs: the edge-pair lists of its first optimize -- rebuild 0: as the call built them (*fused 1:
+ * filled by the first pass against the staged offsets); rebuild 1: built again by the count / scan / fill launches
+ * (the path of sharded handles and of windows beyond the device LM driver).  pp_off [*n_chunks + 1], pp:
+ * {CSR position of the first pose's edge, of the second pose's edge, landmark, 0} per pair.
+ * rspl_ba_debug_final: the inlier flags by the classify kernel's final pass, in the caller's edge order over the
+ * four types; the final state on the device (T_dev [n_poses][8] T_cw: q w x y z, t, pad; X; L) and the T the
+ * final kernel wrote for the host (T_out). */
+int rspl_ba_debug_pairs(rspl_ba* ba, int rebuild, int32_t* pp_off, int cap_off, int32_t* pp, long long cap_pairs,
+                        int* n_chunks, long long* n_pairs, int* fused);
+int rspl_ba_debug_final(rspl_ba* ba, uint8_t* inlier, double* T_dev, double* T_out, double* X, double* L);
 
 /* ------------------------------------------------------------------------ */
 /* Landmark-sharded local BA: nranks handles -- one per  */

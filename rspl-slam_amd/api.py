@@ -388,6 +388,35 @@ class LocalBA:
         a = np.frombuffer(buf, np.float64, n.value * capi.BA_TRACE_W).reshape(n.value, capi.BA_TRACE_W)
         return [dict(zip(capi.BA_TRACE_FIELDS, map(float, row))) for row in a]
 
+    def debug_pairs(self, rebuild=False):
+        """Test hook (rspl_ba_debug_pairs): the Schur chunks' edge-pair lists of the last run() -- (pp_off
+        [chunks + 1], pp [pairs][4], fused) as that call built them, or (rebuild) built again by the count / scan /
+        fill launches."""
+        cap_off, cap = 1 << 16, 1 << 20
+        while True:
+            off, pp = np.zeros(cap_off, np.int32), np.zeros((cap, 4), np.int32)
+            nc, n, fused = C.c_int(), C.c_longlong(), C.c_int()
+            rc = self._lib.rspl_ba_debug_pairs(self._h, 1 if rebuild else 0, off.ctypes.data, cap_off, pp.ctypes.data,
+                                               cap, C.byref(nc), C.byref(n), C.byref(fused))
+            if rc and (nc.value + 1 > cap_off or n.value > cap) and cap < 1 << 26:
+                cap_off, cap = max(cap_off, nc.value + 1), max(cap, int(n.value))
+                continue
+            capi.check(rc, "rspl_ba_debug_pairs")
+            return off[:nc.value + 1].copy(), pp[:n.value].copy(), bool(fused.value)
+
+    def debug_final(self, problem):
+        """Test hook (rspl_ba_debug_final) after run(problem): {"inlier": flags by the classify kernel's final pass in
+        the caller's order over the four edge types, "T_dev" / "points" / "lines": the final device state, "T_out":
+        the poses the final kernel wrote for the host}."""
+        E = sum(problem.n_edges(k) for k in ("mono", "stereo", "mono_line", "stereo_line"))
+        npo, nq, nl = problem.pose_q.shape[0], problem.points.shape[0], problem.lines.shape[0]
+        inl = np.full(max(E, 1), 255, np.uint8)
+        Td, To = np.zeros((max(npo, 1), 8)), np.zeros((max(npo, 1), 8))
+        X, L = np.zeros((max(nq, 1), 3)), np.zeros((max(nl, 1), 6))
+        capi.check(self._lib.rspl_ba_debug_final(self._h, inl.ctypes.data, Td.ctypes.data, To.ctypes.data, X.ctypes.data,
+                                                 L.ctypes.data), "rspl_ba_debug_final")
+        return {"inlier": inl[:E], "T_dev": Td[:npo], "T_out": To[:npo], "points": X[:nq], "lines": L[:nl]}
+
     def use_reserved_cus(self, reserve_cus: int):
         """Confine this handle's kernels to the CUs reserving streams leave free (0 = all CUs)."""
         capi.check(self._lib.rspl_ba_use_reserved_cus(self._h, reserve_cus), "rspl_ba_use_reserved_cus")

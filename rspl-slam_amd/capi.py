@@ -41,6 +41,7 @@ EXPORTS = [
     "rspl_ba_create", "rspl_ba_local", "rspl_ba_submit", "rspl_ba_join", "rspl_ba_destroy", "rspl_ba_use_reserved_cus", "rspl_ba_kernel_timing",
     "rspl_ba_kernel_times", "rspl_ba_trace", "rspl_ba_set_line_jacobian", "rspl_ba_debug_stage",
     "rspl_ba_debug_chunk_plan", "rspl_ba_debug_chunk_geometry",
+    "rspl_ba_debug_pair_offsets", "rspl_ba_debug_pairs", "rspl_ba_debug_final",
     "rspl_frame_create", "rspl_frame_optimize", "rspl_frame_destroy",
     "rspl_ba_set_shard", "rspl_comm_unique_id", "rspl_comm_create", "rspl_comm_allreduce_sum", "rspl_comm_destroy",
     "rspl_ba_set_comm", "rspl_group_create", "rspl_group_destroy", "rspl_ba_set_group",
@@ -309,6 +310,11 @@ def load(path: pathlib.Path = LIB_PATH):
     if hasattr(lib, "rspl_ba_debug_chunk_plan"):  # (absent from older builds used as A/B baselines)
         lib.rspl_ba_debug_chunk_plan.argtypes = [ip, ip, ip, ip, C.POINTER(BaChunkPlan)]
         lib.rspl_ba_debug_chunk_geometry.argtypes = [ip, ip, ip, ip, vp, vp]
+    if hasattr(lib, "rspl_ba_debug_pair_offsets"):  # (absent from older builds used as A/B baselines)
+        lib.rspl_ba_debug_pair_offsets.argtypes = [vp, ip, ip, vp, ip, C.POINTER(ip)]
+        lib.rspl_ba_debug_pairs.argtypes = [vp, ip, vp, ip, vp, C.c_longlong, C.POINTER(ip), C.POINTER(C.c_longlong),
+                                            C.POINTER(ip)]
+        lib.rspl_ba_debug_final.argtypes = [vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "rspl_ba_trace"):  # (absent from older builds used as A/B baselines)
         lib.rspl_ba_trace.argtypes = [vp, C.POINTER(C.c_double), ip, C.POINTER(ip)]
         lib.rspl_ba_set_line_jacobian.argtypes = [vp, ip]

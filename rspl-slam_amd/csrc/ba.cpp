@@ -137,6 +137,18 @@ struct rspl_ba {
   long long trace_n = 0;      // records written since the last read
   unsigned grew = 0;          // device-side buffers grown during the running call (tracking thread)
   int line_jac = 0;           // rspl_ba_set_line_jacobian: 0 g2o's central difference, 1 its analytic limit
+  // what the last completed call left on the device, for the test hooks (rspl_ba_debug_pairs / _final): its
+  // final state and records, its first optimize's structure (the edge-pair lists were built for it), its
+  // CSR -> caller edge map and the T the final kernel wrote into the staging slot
+  struct Last {
+    bool valid = false, fused = false;
+    rspl::ba::Problem P{};
+    rspl::ba::Lin L{};
+    rspl::ba::Active A{};
+    int E = 0;
+    const int* gmap = nullptr;
+    const double* T_out = nullptr;
+  } last;
 };
 
 namespace {
@@ -159,10 +171,11 @@ int allreduce(rspl_ba* b, double* d, size_t n) {
 
 // per-call upload layout (staging call region == device call buffer)
 struct CallLayout {
-  size_t cams, T, X, L, obs, type, pose, lm, cam, gmap, lm_pose, pidx, lm_off, lm_act, pairs, ltab, level, flags, out,
-      bytes;
+  size_t cams, T, X, L, obs, type, pose, lm, cam, gmap, ginv, lm_pose, pidx, lm_off, lm_act, pairs, ltab, pp_off, level,
+      flags, out, bytes;
   CallLayout() = default;
-  CallLayout(int ncam, int np, int nq, int nl, int E, size_t nobs) {  // nobs: observation doubles (4 / 8 per edge)
+  // nobs: observation doubles (4 / 8 per edge); nchunks: Schur chunks of the window (pp_off)
+  CallLayout(int ncam, int np, int nq, int nl, int E, size_t nobs, size_t nchunks) {
     const size_t nL = (size_t)nq + nl;
     size_t so = 0;
     auto place = [&](size_t n) {
@@ -173,6 +186,7 @@ struct CallLayout {
     cams = place(sizeof(double) * 5 * ncam); T = place(sizeof(double) * 8 * np); X = place(sizeof(double) * 3 * nq);
     L = place(sizeof(double) * 6 * nl); obs = place(sizeof(double) * nobs); type = place(E);
     pose = place(4 * (size_t)E); lm = place(4 * (size_t)E); cam = place(4 * (size_t)E); gmap = place(4 * (size_t)E);
+    ginv = place(4 * (size_t)E);  // caller edge id -> CSR position (unsharded calls: the final kernel's flag order)
     lm_pose = place(4 * (size_t)E);
     pidx = place(4 * (size_t)np); lm_off = place(4 * (nL + 1)); lm_act = place(nL);
     pairs = place(8 * (size_t)np * (np + 1) / 2);
@@ -180,6 +194,8 @@ struct CallLayout {
     // landmark with more edges is split) -- sized tight, as the call uploads [0, bytes) in one copy
     const size_t line_edges = nobs >= 4 * (size_t)E ? (nobs - 4 * (size_t)E) / 4 : 0;
     ltab = place(16 * ((size_t)nl + line_edges / ba::kLineBlk + 2));
+    // segment offsets of the Schur chunks' edge-pair lists, counted by the staging (ba::pair_offsets)
+    pp_off = place(4 * (nchunks + 1));
     level = place(E); flags = place(4 * sizeof(int)); out = place(8 * sizeof(double));  // zeros
     bytes = so;
   }
@@ -234,7 +250,8 @@ struct rspl::ba::StagedCall {
   int rc = RSPL_OK;  // staging failed (argument errors): reported when the call's turn comes
   std::string msg;
   int E = 0, Ep = 0, K = 0, n_lblk = 0;
-  size_t pair_bound = 0;
+  size_t pair_bound = 0;   // edge pairs the call's lists must hold (pp_staged: the exact total)
+  bool pp_staged = false;  // cl.pp_off holds the chunks' segment offsets (ba::pair_offsets)
   CallLayout cl;
   DownLayout dl;
   HostMarks tm;
@@ -395,7 +412,7 @@ void report_prof(rspl_ba* b) {
           us(u0, last(ba::kProfUe, nbu, nue, 1)), us(u0, last(ba::kProfUe, nbu, nue, 2)),
           us(u0, last(ba::kProfUe, nbu, nue, 3)), us(h[1], h[5]), us(h[5], h[6]), us(h[6], h[7]), us(h[7], h[8]));
   fprintf(stderr,
-          "ba_prof setup us: landmarks %.1f +pdiag %.1f lines %.1f +pdiag %.1f pairs %.1f | blocks done %.1f scan %.1f "
+          "ba_prof setup us: landmarks %.1f +pdiag %.1f lines %.1f +pdiag %.1f pair fill %.1f | blocks done %.1f cost %.1f "
           "pose diagonals + control %.1f\n",
           us(h[9], h[ba::kProfX]), us(h[9], h[ba::kProfX + 1]), us(h[9], h[ba::kProfX + 2]),
           us(h[9], h[ba::kProfX + 3]), us(h[9], h[ba::kProfX + 4]), us(h[9], h[10]),
@@ -498,7 +515,7 @@ struct SpecFinish {
   bool on = false;
   ba::Lin L{};
   int E = 0;
-  const int* gmap = nullptr;
+  const int* ginv = nullptr;
   uint8_t* inl = nullptr;
   double *Th = nullptr, *Xh = nullptr, *Lh = nullptr;
   unsigned long long q = 0;
@@ -516,6 +533,7 @@ void preupload_next(rspl_ba* b);
 struct DevLmArgs {
   uint8_t* cls_level = nullptr;  // classify the edges into it first (the second optimize's levels)
   bool build_pp = false;         // build the Schur chunks' edge-pair lists (see setup_dev)
+  bool pp_staged = false;        // ... against the offsets the staging counted (else counted on the device)
   SpecFinish* fin = nullptr;
   SpecSetup* nxt = nullptr;
   bool setup_done = false;       // its setup already ran from the speculative queue (SpecSetup)
@@ -546,7 +564,8 @@ int optimize_dev(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, const ba::
     ba::Sys Su = S;  // RSPL_BA_PROF: the first optimize's setup phases too
     Su.prof = b->prof && !b->prof_nb[0] && !cls_level ? b->prof : nullptr;
     RSPL_HIP(ba::setup_dev(P, Lr, A, Su, cls_level, cls_level ? const_cast<uint8_t*>(A.lm_act) : nullptr, iters,
-                           d.build_pp ? b->pp_cnt : nullptr, b->pp_off, b->pp_buf, b->pdg, st));
+                           d.build_pp ? b->pp_buf : nullptr, d.build_pp && !d.pp_staged ? b->pp_cnt : nullptr,
+                           b->pp_off, b->pdg, st));
   }
   unsigned long long q = b->seq;
   const unsigned long long q_first = b->seq + 1;
@@ -567,7 +586,7 @@ int optimize_dev(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, const ba::
         if ((size_t)3 * (b->kev_used + 1) > b->kev.size()) {  // (pre-created by rspl_ba_kernel_timing)
           for (int i = 0; i < 3; i++) {
             hipEvent_t e;
-            RSPL_HIP(hipEventCreate(&e));
+            RSPL_HIP(hipEventCreateWithFlags(&e, kTimingEventFlags));
             b->kev.push_back(e);
           }
           b->grew |= 8;
@@ -596,7 +615,7 @@ int optimize_dev(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, const ba::
       Sf.prof = nullptr;
       fin->q = ++b->seq;
       fin->on = true;
-      RSPL_HIP(ba::finish(P, fin->L, fin->E, fin->gmap, fin->inl, fin->Th, fin->Xh, fin->Lh, Sf, fin->q, st));
+      RSPL_HIP(ba::finish(P, fin->L, fin->E, fin->ginv, fin->inl, fin->Th, fin->Xh, fin->Lh, Sf, fin->q, st));
     }
     return RSPL_OK;
   };
@@ -612,7 +631,7 @@ int optimize_dev(rspl_ba* b, ba::Problem& P, ba::Lin& Lr, ba::Sys& S, const ba::
     S2.prof = nullptr;
     S2.lm_trace = nullptr;
     RSPL_HIP(ba::setup_dev(P, Lr, nxt->A2, S2, nxt->level, const_cast<uint8_t*>(nxt->A2.lm_act), nxt->iters2,
-                           nullptr, b->pp_off, b->pp_buf, b->pdg, st, queued & 1, &Ls, &Ss));
+                           nullptr, nullptr, nullptr, b->pdg, st, queued & 1, &Ls, &Ss));
     nxt->queued = true;
     nxt->extra = false;
     return RSPL_OK;
@@ -790,7 +809,8 @@ extern "C" int rspl_ba_create(const rspl_ba_config* cfg, rspl_ba** out) {
   int prio_lo = 0, prio_hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
   {
-    const size_t cbytes = CallLayout(kMaxCams, b->maxK, cfg->max_points, cfg->max_lines, b->maxE, 8 * (size_t)b->maxE).bytes;
+    const size_t cbytes = CallLayout(kMaxCams, b->maxK, cfg->max_points, cfg->max_lines, b->maxE, 8 * (size_t)b->maxE,
+                                     b->chunk_slots).bytes;
     const char* what = nullptr;
     hipError_t e = hipSuccess;
     auto step = [&](hipError_t r, const char* w) {
@@ -822,7 +842,7 @@ extern "C" int rspl_ba_create(const rspl_ba_config* cfg, rspl_ba** out) {
   // the list still grows on demand, flagged in the call's trace record)
   {
     const size_t sb = std::max(CallLayout(kMaxCams, b->maxK, cfg->max_points, cfg->max_lines, b->maxE,
-                                          8 * (size_t)b->maxE).bytes,
+                                          8 * (size_t)b->maxE, b->chunk_slots).bytes,
                                DownLayout(b->maxK, cfg->max_points, cfg->max_lines, b->maxE).bytes);
     ba::Active Amax{};  // the largest call: every landmark, the most line workgroups
     Amax.nL = b->maxL;
@@ -919,7 +939,8 @@ extern "C" void rspl_ba_destroy(rspl_ba* b) {
 
 namespace {
 int ba_local_impl(rspl_ba* b, const rspl_ba_problem* pr, rspl_ba_result* res);
-int stage_call(rspl_ba* b, int slot, const rspl_ba_problem* pr, rspl_ba_result* res, ba::StagedCall& c);
+int stage_call(rspl_ba* b, int slot, const rspl_ba_problem* pr, rspl_ba_result* res, ba::StagedCall& c,
+               bool off_chain);
 int run_call(rspl_ba* b, const ba::StagedCall& c, const rspl_ba_problem* pr, rspl_ba_result* res, double* tr);
 void push_trace(rspl_ba* b, const double* tr);
 
@@ -961,7 +982,7 @@ extern "C" int rspl_ba_kernel_timing(rspl_ba* b, int every) {
   // plus top-ups after rejected ones; more are created on demand, flagged in the trace record)
   for (size_t n = b->kev.size(); every > 0 && n < 3 * (size_t)kEventTrials; n++) {
     hipEvent_t e;
-    RSPL_HIP(hipEventCreate(&e));
+    RSPL_HIP(hipEventCreateWithFlags(&e, kTimingEventFlags));
     b->kev.push_back(e);
   }
   b->ktime_every = every;
@@ -973,6 +994,60 @@ extern "C" int rspl_ba_set_line_jacobian(rspl_ba* b, int analytic) {
   RSPL_CHECK_ARG(b && (analytic == 0 || analytic == 1), "rspl_ba_set_line_jacobian: NULL handle or mode not 0 / 1");
   RSPL_CHECK_ARG(!queue_active(b), "rspl_ba_set_line_jacobian: calls are queued on the tracking thread (rspl_ba_join first)");
   b->line_jac = analytic;
+  return RSPL_OK;
+}
+
+extern "C" int rspl_ba_debug_pairs(rspl_ba* b, int rebuild, int32_t* pp_off, int cap_off, int32_t* pp, long long cap_pairs,
+                                   int* n_chunks, long long* n_pairs, int* fused) {
+  RSPL_CHECK_ARG(b && pp_off && pp && n_chunks && n_pairs, "rspl_ba_debug_pairs: NULL argument");
+  RSPL_CHECK_ARG(!queue_active(b), "rspl_ba_debug_pairs: calls are queued on the tracking thread (rspl_ba_join first)");
+  RSPL_CHECK_ARG(b->last.valid, "rspl_ba_debug_pairs: no completed unsharded call");
+  ba::Active A = b->last.A;
+  const int nc = ba::chunk_count(A);
+  *n_chunks = nc;
+  *n_pairs = 0;
+  if (fused) *fused = b->last.fused;
+  RSPL_CHECK_ARG(cap_off >= nc + 1, "rspl_ba_debug_pairs: %d offsets, room for %d", nc + 1, cap_off);
+  RSPL_HIP(hipStreamSynchronize(b->stream));
+  if (rebuild) {  // count, scan and fill on the device (the path of the sharded handle and of wide windows)
+    A.pp_off = b->pp_off;
+    RSPL_HIP(ba::build_pairs(A, b->pp_cnt, b->pp_off, b->pp_buf, b->stream));
+    RSPL_HIP(hipStreamSynchronize(b->stream));
+  }
+  pp_off[0] = 0;
+  if (nc == 0) return RSPL_OK;
+  RSPL_HIP(hipMemcpy(pp_off, A.pp_off, sizeof(int) * (nc + 1), hipMemcpyDeviceToHost));
+  *n_pairs = pp_off[nc];
+  RSPL_CHECK_ARG(pp_off[nc] >= 0 && (size_t)pp_off[nc] <= b->pp_cap && *n_pairs <= cap_pairs,
+                 "rspl_ba_debug_pairs: %d pairs, list capacity %zu, room for %lld", pp_off[nc], b->pp_cap, cap_pairs);
+  if (*n_pairs) RSPL_HIP(hipMemcpy(pp, b->pp_buf, sizeof(int4) * (size_t)*n_pairs, hipMemcpyDeviceToHost));
+  return RSPL_OK;
+}
+
+extern "C" int rspl_ba_debug_final(rspl_ba* b, uint8_t* inlier, double* T_dev, double* T_out, double* X, double* L) {
+  RSPL_CHECK_ARG(b && inlier && T_dev && T_out && X && L, "rspl_ba_debug_final: NULL argument");
+  RSPL_CHECK_ARG(!queue_active(b), "rspl_ba_debug_final: calls are queued on the tracking thread (rspl_ba_join first)");
+  RSPL_CHECK_ARG(b->last.valid, "rspl_ba_debug_final: no completed unsharded call");
+  const ba::Problem& P = b->last.P;
+  const int E = b->last.E;
+  RSPL_HIP(hipStreamSynchronize(b->stream));
+  if (E) {  // the classify kernel's final pass: one flag per CSR position, carried to the caller's order here
+    uint8_t* d = nullptr;
+    RSPL_HIP(hipMalloc((void**)&d, E));
+    std::vector<uint8_t> f(E);
+    std::vector<int> gmap(E);
+    hipError_t e = ba::classify(P, b->last.L, E, nullptr, d, 1, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = hipMemcpy(f.data(), d, E, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(gmap.data(), b->last.gmap, sizeof(int) * E, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    RSPL_HIP(e);
+    for (int k = 0; k < E; k++) inlier[gmap[k]] = f[k];
+  }
+  if (P.np) RSPL_HIP(hipMemcpy(T_dev, P.T, sizeof(double) * 8 * P.np, hipMemcpyDeviceToHost));
+  if (P.nq) RSPL_HIP(hipMemcpy(X, P.X, sizeof(double) * 3 * P.nq, hipMemcpyDeviceToHost));
+  if (P.nl) RSPL_HIP(hipMemcpy(L, P.L, sizeof(double) * 6 * P.nl, hipMemcpyDeviceToHost));
+  std::copy(b->last.T_out, b->last.T_out + 8 * (size_t)P.np, T_out);
   return RSPL_OK;
 }
 
@@ -1045,7 +1120,7 @@ void staging_loop(rspl_ba* b) {
     lk.unlock();
     sc->slot = slot;
     sc->tr[1] = mono_s();
-    sc->rc = stage_call(b, slot, pr, res, *sc);
+    sc->rc = stage_call(b, slot, pr, res, *sc, true);
     sc->tr[2] = mono_s();
     sc->tr[8] = slot;
     if (sc->rc) sc->msg = rspl_last_error();
@@ -1231,10 +1306,45 @@ extern "C" int rspl_ba_debug_stage(const rspl_ba_problem* pr, int par_edges, int
   return RSPL_OK;
 }
 
+extern "C" int rspl_ba_debug_pair_offsets(const rspl_ba_problem* pr, int max_landmarks, int max_poses, int32_t* pp_off,
+                                          int cap, int* n_chunks) {
+  RSPL_CHECK_ARG(pr && pp_off && n_chunks, "rspl_ba_debug_pair_offsets: NULL argument");
+  RSPL_CHECK_ARG(pr->n_poses >= 0 && pr->n_points >= 0 && pr->n_lines >= 0 && pr->n_mono >= 0 &&
+                     pr->n_stereo >= 0 && pr->n_mono_line >= 0 && pr->n_stereo_line >= 0 &&
+                     (pr->n_poses == 0 || pr->pose_fixed) && pr->n_cameras >= 1,
+                 "rspl_ba_debug_pair_offsets: bad problem sizes");
+  const int nL = pr->n_points + pr->n_lines;
+  RSPL_CHECK_ARG(max_landmarks >= nL && max_poses >= pr->n_poses, "rspl_ba_debug_pair_offsets: window beyond the handle");
+  ba::Stager stg;
+  int rc;
+  if ((rc = stg.count(pr, false, 0, 1, 0))) return rc;
+  const int E = stg.E;
+  std::vector<int> pidx(pr->n_poses);
+  ba::Active G{};
+  for (int p = 0; p < pr->n_poses; p++) pidx[p] = (stg.pose_has_edge[p] && !pr->pose_fixed[p]) ? G.K++ : -1;
+  std::vector<int> lm_off(nL + 1), epose(E + 1), elm(E + 1), ecam(E + 1), gmap(E + 1), lpose(E + 1);
+  std::vector<int8_t> etype(E + 1);
+  std::vector<double> eobs(8 * (size_t)E + 8);
+  std::vector<uint8_t> lm_act(nL + 1);
+  ba::Stager::Out so{lm_off.data(), etype.data(), epose.data(), elm.data(), ecam.data(),
+                     gmap.data(),   lpose.data(), eobs.data(),  pidx.data()};
+  stg.place(pr, so);
+  for (int g = 0; g < nL; g++) lm_act[g] = lm_off[g + 1] > lm_off[g];
+  G.npairs = G.K * (G.K + 1) / 2;
+  G.nL = nL;
+  const ba::ChunkPlan cp = ba::chunk_plan(nL, G.K, ba::chunk_slots_for(max_landmarks, max_poses));
+  G.nchk = cp.nchk; G.lmchunk = cp.lmchunk; G.dsub = cp.dsub; G.lmsub = cp.lmsub;
+  *n_chunks = ba::chunk_count(G);
+  RSPL_CHECK_ARG(cap >= *n_chunks + 1, "rspl_ba_debug_pair_offsets: %d offsets, room for %d", *n_chunks + 1, cap);
+  ba::pair_offsets(G, lm_off.data(), lpose.data(), lm_act.data(), pp_off);
+  return RSPL_OK;
+}
+
 namespace {
 // Host staging of one call into stage slot `slot` (inputs only: nothing touches the device or the
 // stream in steady state, so the tracking thread's next call is staged while the current one runs)
-int stage_call(rspl_ba* b, int slot, const rspl_ba_problem* pr, rspl_ba_result* res, ba::StagedCall& c) {
+int stage_call(rspl_ba* b, int slot, const rspl_ba_problem* pr, rspl_ba_result* res, ba::StagedCall& c,
+               bool off_chain) {
   RSPL_CHECK_ARG(b && pr && res, "rspl_ba_local: NULL argument");
   const int np = pr->n_poses, nq = pr->n_points, nl = pr->n_lines;
   const int ne[4] = {pr->n_mono, pr->n_stereo, pr->n_mono_line, pr->n_stereo_line};
@@ -1257,7 +1367,19 @@ int stage_call(rspl_ba* b, int slot, const rspl_ba_problem* pr, rspl_ba_result* 
   if ((rc = b->stg.count(pr, sh, b->rank, b->nranks, kParEdges))) return rc;
   const int E = b->stg.E, Ep = b->stg.Ep, n_line_local = E - Ep;
   tm.mark("count");
-  const CallLayout cl(pr->n_cameras, np, nq, nl, E, 4 * (size_t)Ep + 8 * (size_t)(E - Ep));
+  // the window's Schur chunk geometry (run_call's A carries the same plan)
+  ba::Active G{};
+  for (int p = 0; p < np; p++) G.K += b->stg.pose_has_edge[p] && !pr->pose_fixed[p];
+  G.npairs = G.K * (G.K + 1) / 2;
+  G.nL = nL;
+  {
+    const ba::ChunkPlan cp = ba::chunk_plan(nL, G.K, b->chunk_slots);
+    G.nchk = cp.nchk;
+    G.lmchunk = cp.lmchunk;
+    G.dsub = cp.dsub;
+    G.lmsub = cp.lmsub;
+  }
+  const CallLayout cl(pr->n_cameras, np, nq, nl, E, 4 * (size_t)Ep + 8 * (size_t)(E - Ep), (size_t)ba::chunk_count(G));
   const DownLayout dl(np, nq, nl, Eg);  // inlier flags by global edge id
   bool grew = false;
   if ((rc = ensure_stage(b, slot, std::max(cl.bytes, dl.bytes), &grew))) return rc;
@@ -1297,6 +1419,7 @@ int stage_call(rspl_ba* b, int slot, const rspl_ba_problem* pr, rspl_ba_result* 
     so.lpose = reinterpret_cast<int*>(sg + cl.lm_pose);
     so.eobs = reinterpret_cast<double*>(sg + cl.obs);
     so.pidx = pidx;
+    so.ginv = sh ? nullptr : reinterpret_cast<int*>(sg + cl.ginv);  // (the final kernel's flag order: unsharded calls)
     b->stg.place(pr, so);
   }
   tm.mark("scatter");
@@ -1344,6 +1467,15 @@ int stage_call(rspl_ba* b, int slot, const rspl_ba_problem* pr, rspl_ba_result* 
       pairs[2 * q + 1] = c;
     }
   tm.mark("tables");
+  // the fused first pass (device LM, unsharded: run_call's pp_fused) fills the Schur chunks' edge-pair lists
+  // against offsets counted here when this runs off the device's chain (the staging thread: the count costs
+  // about as much as the rest of the staging, a call staged on its own chain counts on the device as before);
+  // the exact total sizes the list
+  c.pp_staged = off_chain && !sh && pr->iterations_first > 0 && ba::fast_path(G.K);
+  if (c.pp_staged)
+    pair_bound = ba::pair_offsets(G, lm_off, reinterpret_cast<const int*>(sg + cl.lm_pose), lm_act,
+                                  reinterpret_cast<int*>(sg + cl.pp_off));
+  tm.mark("ppoff");
   memcpy(sg + cl.cams, pr->cameras, sizeof(double) * 5 * pr->n_cameras);
   if (nq) memcpy(sg + cl.X, pr->points, sizeof(double) * 3 * nq);
   if (nl) memcpy(sg + cl.L, pr->lines, sizeof(double) * 6 * nl);
@@ -1463,15 +1595,20 @@ int run_call(rspl_ba* b, const ba::StagedCall& c, const rspl_ba_problem* pr, rsp
   A.K = K;
   A.nL = nL;
   A.robust = 1;
-  A.pp_off = b->pp_off;
+  A.pp_off = c.pp_staged ? reinterpret_cast<const int*>(cb + cl.pp_off) : b->pp_off;
   A.pp = b->pp_buf;
   // on the BA stream itself: a second stream would take a hardware queue of its own (streams map
   // round-robin onto GPU_MAX_HW_QUEUES) and push a pipeline stream onto the BA's queue -- measured:
   // bench 2.17 ms per step instead of 1.5 with a side stream for the pair lists
-  const bool pp_fused = dev_lm(b, A, pr->iterations_first);  // else: built here, before the first optimize
+  // device LM: the first pass builds the lists (against the staged offsets when the staging thread counted
+  // them); else (the sharded handle, windows beyond the fast path): counted, scanned and filled here
+  const bool pp_fused = dev_lm(b, A, pr->iterations_first);
   if (!pp_fused) RSPL_HIP(ba::build_pairs(A, b->pp_cnt, b->pp_off, b->pp_buf, st));
   tm.mark("pairs");
   // phase 2's setup queued behind phase 1's trials (device LM on both, unsharded)
+  b->last.valid = false;
+  b->last.A = A;
+  b->last.fused = pp_fused && c.pp_staged;
   SpecSetup nxt;
   nxt.A2 = A;
   nxt.A2.robust = 0;
@@ -1482,6 +1619,7 @@ int run_call(rspl_ba* b, const ba::StagedCall& c, const rspl_ba_problem* pr, rsp
   const bool spec_setup = pp_fused && !sh && !b->ktime_on && dev_lm(b, nxt.A2, pr->iterations_second);
   DevLmArgs d1;
   d1.build_pp = pp_fused;
+  d1.pp_staged = c.pp_staged;
   d1.nxt = spec_setup ? &nxt : nullptr;
   if ((rc = optimize(b, P, Lr, S, A, pr->iterations_first, &res->chi2_first, &res->iterations_done_first, d1)))
     return rc;
@@ -1511,7 +1649,7 @@ int run_call(rspl_ba* b, const ba::StagedCall& c, const rspl_ba_problem* pr, rsp
     if (spec_fin) {
       fin.L = Lr;
       fin.E = E;
-      fin.gmap = reinterpret_cast<const int*>(cb + cl.gmap);
+      fin.ginv = reinterpret_cast<const int*>(cb + cl.ginv);
       fin.inl = inl_h;
       fin.Th = T_h;
       fin.Xh = X_h;
@@ -1541,7 +1679,7 @@ int run_call(rspl_ba* b, const ba::StagedCall& c, const rspl_ba_problem* pr, rsp
     if (glen && (rc = allreduce(b, b->gbuf, glen))) return rc;
     RSPL_HIP(ba::shard_finish(P, Eg, b->gbuf, inl_h, T_h, X_h, L_h, S, q, st));
   } else {
-    RSPL_HIP(ba::finish(P, Lr, E, reinterpret_cast<const int*>(cb + cl.gmap), inl_h, T_h, X_h, L_h, S, q, st));
+    RSPL_HIP(ba::finish(P, Lr, E, reinterpret_cast<const int*>(cb + cl.ginv), inl_h, T_h, X_h, L_h, S, q, st));
   }
   if ((rc = wait_mail(b, q, nullptr))) return rc;
   if (b->ktime_on) {  // every timed trial precedes the finish kernel in the stream: its events are complete
@@ -1589,6 +1727,12 @@ int run_call(rspl_ba* b, const ba::StagedCall& c, const rspl_ba_problem* pr, rsp
     res->pose_q[4 * p + 3] = Twc.q[0];
     for (int k = 0; k < 3; k++) res->pose_p[3 * p + k] = Twc.t[k];
   }
+  b->last.P = P;
+  b->last.L = Lr;
+  b->last.E = E;
+  b->last.gmap = reinterpret_cast<const int*>(cb + cl.gmap);
+  b->last.T_out = Tout;
+  b->last.valid = !sh;
   tm.mark("final");
   tm.print("rspl_ba_local us:");
   tr[7] = mono_s();
@@ -1601,7 +1745,7 @@ int ba_local_impl(rspl_ba* b, const rspl_ba_problem* pr, rspl_ba_result* res) {
   ba::StagedCall c;
   c.tr[0] = c.tr[1] = mono_s();
   c.tr[11] = 1;
-  int rc = stage_call(b, 0, pr, res, c);
+  int rc = stage_call(b, 0, pr, res, c, false);  // (staged on the call's own chain)
   c.tr[2] = c.tr[3] = mono_s();
   if (!rc) rc = run_call(b, c, pr, res, c.tr);
   if (!rc) {

@@ -213,6 +213,8 @@ __device__ __forceinline__ void pair_scan(const Active& A, int c, int* pp_cnt, c
   }
   const int pa = A.pairs[2 * pr], pb = A.pairs[2 * pr + 1];
   int base = FILL ? pp_off[c] : 0;
+  const int lim = FILL ? pp_off[c + 1] : 0;  // the segment's end: offsets counted elsewhere (the host staging) never
+                                             // let a store leave the chunk's segment
   // four landmark rounds at a time: their CSR ranges, then the first eight edge poses of each (a landmark's
   // whole edge list when it has <= 8 edges, the common case), every load of a group in flight at once
   for (int r0 = 0; r0 < nr; r0 += 4) {
@@ -271,7 +273,8 @@ __device__ __forceinline__ void pair_scan(const Active& A, int c, int* pp_cnt, c
         int q = base + pre - cnt;
         for (unsigned ma = ma1; ma; ma &= ma - 1) {
           const int ea = (e0 + __ffs(ma) - 1);
-          for (unsigned mb = mb1; mb; mb &= mb - 1) pp[q++] = make_int4(ea, (e0 + __ffs(mb) - 1), g, 0);
+          for (unsigned mb = mb1; mb; mb &= mb - 1, q++)
+            if (q < lim) pp[q] = make_int4(ea, (e0 + __ffs(mb) - 1), g, 0);
         }
       } else if (FILL && cnt) {
         int q = base + pre - cnt;
@@ -279,7 +282,7 @@ __device__ __forceinline__ void pair_scan(const Active& A, int c, int* pp_cnt, c
           if (A.lm_pose[ib] != pa) continue;
           for (int jb = e0; jb < e1; jb++) {
             if (A.lm_pose[jb] != pb) continue;
-            pp[q] = make_int4(ib, jb, g, 0);
+            if (q < lim) pp[q] = make_int4(ib, jb, g, 0);
             q++;
           }
         }
@@ -403,13 +406,14 @@ __device__ __forceinline__ void prof_max(const Sys& S, int slot) {  // latest ov
 }
 
 // The first pass in ONE launch: blocks [0, nbq) landmark groups, [nbq, nb_lm) line workgroups,
-// [nb_lm, ...) pair counting; every landmark / line block then sums the pose diagonals of its own
-// edges (pose_diag_range -> pdg) and every block takes a ticket; the last block sums the cost
-// partials and the pose-diagonal partials in block order, scans the pair counts and writes the LM
+// [nb_lm, ...) the edge-pair lists' fill (or count); every landmark / line block then sums the pose diagonals of
+// its own edges (pose_diag_range -> pdg) and every block takes a ticket; the last block sums the cost
+// partials and the pose-diagonal partials in block order, scans the pair counts (if counted here) and writes the LM
 // control (round 3 did this in a second launch; one launch measured neutral, four per call instead of six).
 __global__ __launch_bounds__(256) void setup_kernel(Problem P, Lin L, Active A, Sys S, int nbq, int nb_lm,
-                                                    uint8_t* level, uint8_t* lm_act2, int* pp_cnt, int* pp_off,
-                                                    double* pdg, int lm_iters, int gate, Lin Ls, Sys Ss) {
+                                                    uint8_t* level, uint8_t* lm_act2, int4* pp_fill, int* pp_cnt,
+                                                    int* pp_off, double* pdg, int lm_iters, int gate, Lin Ls,
+                                                    Sys Ss) {
   __shared__ double red[4];
   __shared__ double part[4][64];
   __shared__ int last;
@@ -423,9 +427,14 @@ __global__ __launch_bounds__(256) void setup_kernel(Problem P, Lin L, Active A, 
   }
   const int b = blockIdx.x;
   if (b == 0 && threadIdx.x == 0) prof_stamp(S, 9);
-  if (b >= nb_lm) {  // the first optimize: edge pairs per Schur chunk, one wave per chunk
+  if (b >= nb_lm) {  // the first optimize: the Schur chunks' edge-pair lists, one wave per chunk -- filled
+                     // against the offsets the host staging counted (pp_fill; A.pp_off: in the call's upload),
+                     // or only counted (pp_cnt: a call staged on its own chain; scanned below, filled by a launch)
     const int c = (b - nb_lm) * 4 + (threadIdx.x >> 6);
-    if (c < chunk_count(A)) pair_scan<false>(A, c, pp_cnt, nullptr, nullptr);
+    if (c < chunk_count(A)) {
+      if (pp_fill) pair_scan<true>(A, c, nullptr, A.pp_off, pp_fill);
+      else pair_scan<false>(A, c, pp_cnt, nullptr, nullptr);
+    }
     if (threadIdx.x == 0) prof_max(S, kProfX + 4);
   } else if (b >= nbq) {
     double c = 0.0;  // set in thread 0
@@ -566,10 +575,15 @@ __global__ __launch_bounds__(256) void classify_kernel(Problem P, Lin L, int E, 
 }
 
 // end of a call: final inlier flags + the final T / X / L written straight into host-mapped
-// memory; the last block (ticket) posts the mailbox once every block's writes are out
-__global__ __launch_bounds__(256) void finish_kernel(Problem P, Lin L, int E, const int* gmap, uint8_t* inl, double* Th,
+// memory; the last block (ticket) posts the mailbox once every block's writes are out.  Everything crosses
+// PCIe as 16-byte stores: a block owns 256 consecutive flags of the caller's order -- thread t classifies the
+// edge behind flag 256 b + t (ginv: caller edge id -> CSR position, scattered device reads), 16 threads then
+// store the block's flags (inl is padded to 256 bytes: the last word's bytes past E are zeros) -- and a
+// thread two doubles of T / X / L.
+__global__ __launch_bounds__(256) void finish_kernel(Problem P, Lin L, int E, const int* ginv, uint8_t* inl, double* Th,
                                                      double* Xh, double* Lh, Sys S, unsigned long long seq) {
   __shared__ int last;
+  __shared__ uint4 fl4[16];
   if (S.lm) {  // queued behind the last optimize()'s trials (S.lm_slot: the control after the last one):
                // a no-op unless that optimize() has stopped; the current bank from its control
     const LmCtrl* c = S.lm + S.lm_slot;
@@ -577,10 +591,17 @@ __global__ __launch_bounds__(256) void finish_kernel(Problem P, Lin L, int E, co
     if (c->cur) bank_state(P);
   }
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < E) inl[gmap[i]] = edge_inlier(P, L, i) ? 1 : 0;
-  if (i < 8 * P.np) Th[i] = P.T[i];
-  if (i < 3 * P.nq) Xh[i] = P.X[i];
-  if (i < 6 * P.nl) Lh[i] = P.L[i];
+  reinterpret_cast<uint8_t*>(fl4)[threadIdx.x] = i < E && edge_inlier(P, L, ginv[i]) ? 1 : 0;
+  auto put2 = [i](double* dst, const double* src, int n) {
+    if (2 * i + 1 < n) *reinterpret_cast<double2*>(dst + 2 * i) = make_double2(src[2 * i], src[2 * i + 1]);
+    else if (2 * i < n) dst[2 * i] = src[2 * i];
+  };
+  put2(Th, P.T, 8 * P.np);
+  put2(Xh, P.X, 3 * P.nq);
+  put2(Lh, P.L, 6 * P.nl);
+  __syncthreads();
+  if (threadIdx.x < 16 && blockIdx.x * 256 + 16 * (int)threadIdx.x < E)
+    reinterpret_cast<uint4*>(inl)[blockIdx.x * 16 + threadIdx.x] = fl4[threadIdx.x];
   __threadfence_system();
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -688,19 +709,22 @@ int setup_pdg_len(const Active& A) {
 }
 
 hipError_t setup_dev(const Problem& P, const Lin& L, const Active& A, Sys& S, uint8_t* level, uint8_t* lm_act2,
-                     int lm_iters, int* pp_cnt, int* pp_off, int4* pp, double* pdg, hipStream_t s, int gate,
+                     int lm_iters, int4* pp, int* pp_cnt, int* pp_off, double* pdg, hipStream_t s, int gate,
                      const Lin* Ls, const Sys* Ss) {
-  if (gate >= 0 && (!Ls || !Ss || pp_cnt)) return hipErrorInvalidValue;
+  if (gate >= 0 && (!Ls || !Ss || pp)) return hipErrorInvalidValue;
+  if (pp_cnt && !pp_off) return hipErrorInvalidValue;
   if (!S.lm || lm_iters <= 0) return hipErrorInvalidValue;
   Active A0 = A;
   A0.elevel = nullptr;  // the levels are written by this launch (level != null), never read by it
   const int nc = chunk_count(A);
-  if (nc == 0) pp_cnt = nullptr;
+  if (nc == 0) pp = nullptr;
+  if (!pp) pp_cnt = nullptr;
+  int4* const pp_fill = pp_cnt ? nullptr : pp;  // staged offsets: the first pass fills the lists itself
   const int nbq = A.nL > 0 ? (A.nL * kGroup + 255) / 256 : 0, nb = nbq + A.n_lblk;
-  const int nbp = pp_cnt ? (nc + 3) / 4 : 0;
+  const int nbp = pp ? (nc + 3) / 4 : 0;
   // at least one block: the last one writes the LM control
   hipLaunchKernelGGL(setup_kernel, dim3(std::max(nb + nbp, 1)), dim3(256), 0, s, P, L, A0, S, nbq, nb, level, lm_act2,
-                     pp_cnt, pp_off, pdg, lm_iters, gate, Ls ? *Ls : L, Ss ? *Ss : S);
+                     pp_fill, pp_cnt, pp_off, pdg, lm_iters, gate, Ls ? *Ls : L, Ss ? *Ss : S);
   if (pp_cnt) hipLaunchKernelGGL(pair_fill_kernel, dim3(nc), dim3(64), 0, s, A, pp_off, pp);
   return hipGetLastError();
 }
@@ -711,10 +735,10 @@ hipError_t post(Sys& S, unsigned long long seq, hipStream_t s, const Active* A) 
   return hipGetLastError();
 }
 
-hipError_t finish(const Problem& P, const Lin& L, int E, const int* gmap, uint8_t* inl, double* Th, double* Xh,
+hipError_t finish(const Problem& P, const Lin& L, int E, const int* ginv, uint8_t* inl, double* Th, double* Xh,
                   double* Lh, Sys& S, unsigned long long seq, hipStream_t s) {
-  const int n = std::max(std::max(E, 8 * P.np), std::max(3 * P.nq, 6 * P.nl));
-  hipLaunchKernelGGL(finish_kernel, dim3(std::max((n + 255) / 256, 1)), dim3(256), 0, s, P, L, E, gmap, inl, Th, Xh,
+  const int n = std::max(std::max(E, 4 * P.np), std::max((3 * P.nq + 1) / 2, 3 * P.nl));  // a flag / two doubles each
+  hipLaunchKernelGGL(finish_kernel, dim3(std::max((n + 255) / 256, 1)), dim3(256), 0, s, P, L, E, ginv, inl, Th, Xh,
                      Lh, S, seq);
   return hipGetLastError();
 }

@@ -244,15 +244,18 @@ hipError_t post(Sys& S, unsigned long long seq, hipStream_t s, const Active* A =
 // cost and linearisation at the current state, the pose / landmark diagonal maximum and the LM control
 // (computeLambdaInit) into S.lm[0].  level != null (the second optimize): the edges' outlier levels
 // from their last computed errors into level[] and the landmark activity into lm_act2 first (replaces
-// classify + landmark_active); A.elevel / A.lm_act are then the caller's level / lm_act2.  pp_cnt
-// != null (the call's first optimize): the Schur chunks' edge-pair lists too (replaces build_pairs:
-// counted in the first launch, scanned by the second's last block, filled by a third).
+// classify + landmark_active); A.elevel / A.lm_act are then the caller's level / lm_act2.  pp
+// != null (the call's first optimize): the Schur chunks' edge-pair lists too (replaces build_pairs).  pp_cnt
+// null: filled into pp by waves of the same launch against A.pp_off -- the segment offsets the host staging
+// counted off the call's chain (ba::pair_offsets), part of the call's upload.  pp_cnt != null (a call staged on
+// its own chain, rspl_ba_local: a host count would cost it more than it saves): counted in the launch, scanned
+// into pp_off by its last block, filled by a second launch.
 // pdg: setup_pdg_len(A) doubles of per-block pose-diagonal partials.
 // gate >= 0 (the second optimize's setup queued behind the first one's trials before the host has seen them):
 // a no-op unless the control slot `gate` shows that optimize stopped; then the current bank from that control
 // (Ls / Ss: the spare records, as the trials bank them)
 hipError_t setup_dev(const Problem& P, const Lin& L, const Active& A, Sys& S, uint8_t* level, uint8_t* lm_act2,
-                     int lm_iters, int* pp_cnt, int* pp_off, int4* pp, double* pdg, hipStream_t s, int gate = -1,
+                     int lm_iters, int4* pp, int* pp_cnt, int* pp_off, double* pdg, hipStream_t s, int gate = -1,
                      const Lin* Ls = nullptr, const Sys* Ss = nullptr);
 int setup_pdg_len(const Active& A);
 // speculative linearisation of a trial's candidate into a spare record set, fused into the
@@ -278,8 +281,9 @@ hipError_t build_pairs(const Active& A, int* pp_cnt, int* pp_off, int4* pp, hipS
 hipError_t landmark_active(const Active& A, const uint8_t* level, uint8_t* lm_act, hipStream_t s);
 hipError_t classify(const Problem& P, const Lin& L, int E, uint8_t* level, uint8_t* inlier, int final_pass,
                     hipStream_t s);
-// final inlier flags + T / X / L into host-mapped memory, then the mailbox post of seq
-hipError_t finish(const Problem& P, const Lin& L, int E, const int* gmap, uint8_t* inl, double* Th, double* Xh,
+// final inlier flags + T / X / L into host-mapped memory, then the mailbox post of seq.  ginv: caller edge id ->
+// CSR position [E]; inl (the caller's order) is written in 16-byte words: room for E rounded up to 16
+hipError_t finish(const Problem& P, const Lin& L, int E, const int* ginv, uint8_t* inl, double* Th, double* Xh,
                   double* Lh, Sys& S, unsigned long long seq, hipStream_t s);
 // ---- landmark-sharded pieces (rspl_ba_set_shard): the host interleaves the all-reduces ----
 // trial, part 1: Schur chunks of this rank's edge pairs -> pairfin; the landmark-inversion flag

@@ -167,6 +167,7 @@ void Stager::place(const rspl_ba_problem* pr, const Out& o) {
   const int nq = pr->n_points, nL = nq + pr->n_lines;
   int* lm_off = o.lm_off;
   int* gmap = o.gmap;
+  int* ginv = o.ginv;
   const int* pidx = o.pidx;
   const int Ep_ = Ep;
   double* lobs = o.eobs + 4 * (size_t)Ep_;
@@ -177,6 +178,7 @@ void Stager::place(const rspl_ba_problem* pr, const Out& o) {
     static const double zero = 0.0;
     for (int k = k0; k < std::min(k1, Ep_); k++) {
       const int eg = gmap[k];
+      if (ginv) ginv[eg] = k;
       const bool st = eg >= e1;
       const int i = st ? eg - e1 : eg;
       const int32_t* pt = st ? ed.pose[1] : ed.pose[0];
@@ -195,6 +197,7 @@ void Stager::place(const rspl_ba_problem* pr, const Out& o) {
     }
     for (int k = std::max(k0, Ep_); k < k1; k++) {
       const int eg = gmap[k];
+      if (ginv) ginv[eg] = k;
       const int t = eg >= e3 ? 3 : 2;
       const int i = eg - (t == 3 ? e3 : e2);
       const int p = ed.pose[t][i];
@@ -247,6 +250,45 @@ void Stager::place(const rspl_ba_problem* pr, const Out& o) {
     }
   }
   gather(0, E);
+}
+
+size_t pair_offsets(const Active& G, const int* lm_off, const int* lm_pose, const uint8_t* lm_act, int* pp_off) {
+  const int nc = chunk_count(G), K = G.K;
+  // scratch kept across calls (the staging thread's); the counts are summed here, not in the caller's buffer
+  // (the staging slot is host-mapped memory)
+  static thread_local std::vector<int> n, first, cnt, seen;
+  n.assign((size_t)nc + 1, 0);
+  // first chunk of every pose pair, from the chunk geometry itself (pairs are numbered row-major over a <= b)
+  first.assign(std::max(G.npairs, 1), 0);
+  for (int c = 0; c < nc;) {
+    const ChunkGeo q = chunk_geo(G, c);
+    first[q.pr] = q.c0;
+    c = q.c1;
+  }
+  // per landmark: its edges per reduced pose, over the poses it has (cnt / seen reset after each landmark)
+  cnt.assign(std::max(K, 1), 0);
+  for (int g = 0; g < G.nL; g++) {
+    if (!lm_act[g]) continue;
+    seen.clear();
+    for (int k = lm_off[g]; k < lm_off[g + 1]; k++) {
+      const int p = lm_pose[k];
+      if (p >= 0 && cnt[p]++ == 0) seen.push_back(p);
+    }
+    const int lb = g / G.lmchunk;
+    const int sub = G.dsub > 1 ? lb * G.dsub + (g - lb * G.lmchunk) / G.lmsub : lb;  // a diagonal pair's chunk
+    for (size_t i = 0; i < seen.size(); i++) {
+      const int a = seen[i];
+      n[first[a * K - a * (a - 1) / 2] + sub + 1] += cnt[a] * cnt[a];
+      for (size_t j = i + 1; j < seen.size(); j++) {  // the pair (lo <= hi), whichever the landmark met first
+        const int lo = std::min(a, seen[j]), hi = std::max(a, seen[j]);
+        n[first[lo * K - lo * (lo - 1) / 2 + hi - lo] + lb + 1] += cnt[lo] * cnt[hi];
+      }
+    }
+    for (const int p : seen) cnt[p] = 0;
+  }
+  for (int c = 0; c < nc; c++) n[c + 1] += n[c];  // counts at [c + 1] -> exclusive scan
+  std::copy(n.begin(), n.end(), pp_off);
+  return (size_t)n[nc];
 }
 
 }  // namespace ba

@@ -9,6 +9,7 @@
 #include <memory>
 #include <vector>
 
+#include "ba_kernels.hpp"
 #include "common.hpp"
 #include "host_pool.hpp"
 
@@ -23,7 +24,7 @@ struct Stager {
   int count(const rspl_ba_problem* pr, bool sharded, int rank, int nranks, int par_edges);
   // pass 2: lm_off [nL + 1] and, per CSR position k < E, the edge's type, pose, landmark, camera,
   // caller id (gmap), reduced pose (pidx of its pose) and observation (points: 4 doubles each from
-  // eobs; lines: 8 doubles each from eobs + 4 Ep)
+  // eobs; lines: 8 doubles each from eobs + 4 Ep); ginv (or null): the CSR position of every caller id
   struct Out {
     int* lm_off;
     int8_t* etype;
@@ -34,6 +35,7 @@ struct Stager {
     int* lpose;
     double* eobs;
     const int* pidx;
+    int* ginv = nullptr;
   };
   void place(const rspl_ba_problem* pr, const Out& o);
 
@@ -51,6 +53,13 @@ struct Stager {
   std::vector<int> pcut_, gcut_, rstart_;    // part p: caller edges [pcut[p], pcut[p+1]); range q:
                                              //   landmarks [gcut[q], gcut[q+1]), CSR [rstart[q], rstart[q+1])
 };
+
+// Segment offsets of the Schur chunks' edge-pair lists, counted on the host from the staged CSR: chunk c of
+// pose pair (a <= b) and a landmark range owns sum over its active landmarks of cnt_g[a] * cnt_g[b] pairs
+// (cnt_g[p]: the landmark's edges on reduced pose p; -1 entries of lm_pose are on no reduced pose), exactly what
+// pair_scan counts on the device.  G: nchk / lmchunk / dsub / lmsub / K / npairs / nL set (chunk_geo's fields).
+// pp_off [chunk_count(G) + 1]: the exclusive scan; returns the total.
+size_t pair_offsets(const Active& G, const int* lm_off, const int* lm_pose, const uint8_t* lm_act, int* pp_off);
 
 }  // namespace ba
 }  // namespace rspl

@@ -115,6 +115,17 @@ struct Sizer {
   }
 };
 
+// The three classes of HIP event in this library (DESIGN.md section 7 lists every event).  A record of an event
+// created with default flags ends in a system-scope release: a write-back of the L2s that every queue of the
+// device shares, paid by whatever runs beside it.
+//   timing: only hipEventElapsedTime reads it; no data is handed over through it.
+//   order:  recorded on one stream and waited on by another stream of the same device (or synchronised by the
+//           host only to know that the device is done with a buffer): a device-scope release orders that.
+//   host:   the host reads device-written memory after synchronising on it: the default (system) scope.
+constexpr unsigned kTimingEventFlags = hipEventDisableSystemFence;
+constexpr unsigned kOrderEventFlags = hipEventDisableTiming | hipEventReleaseToDevice;
+constexpr unsigned kHostEventFlags = hipEventDisableTiming;
+
 // Per-stage device timing: HIP events recorded on the launch stream at stage
 // boundaries of each profiled call, kept in a ring and harvested lazily so the
 // profiling never adds a host synchronisation to the pipeline.
@@ -131,7 +142,7 @@ struct StageTimer {
     n = nstages;
     for (int r = 0; r < kRing; r++)
       for (int i = 0; i <= n; i++)
-        if (hipEventCreate(&ev[r][i]) != hipSuccess) return RSPL_E_DEVICE;
+        if (hipEventCreateWithFlags(&ev[r][i], kTimingEventFlags) != hipSuccess) return RSPL_E_DEVICE;
     return RSPL_OK;
   }
   void destroy() {
@@ -188,6 +199,9 @@ int load_blob(const char* path, std::vector<Tensor>& out);
 // bytes from host-mapped pinned memory (src_mapped: its device pointer) into device memory by a copy
 // kernel on stream s (copy_kernels.hip)
 hipError_t upload_mapped(void* dst, const void* src_mapped, size_t bytes, hipStream_t s);
+// bytes between two buffers of the current device by a copy kernel on stream s: any byte count, any alignment
+// (the widest of 16 / 8 / 4 / 1-byte accesses that both addresses allow)
+hipError_t copy_device(void* dst, const void* src, size_t bytes, hipStream_t s);
 const Tensor* find(const std::vector<Tensor>& ts, const std::string& name, int64_t numel);
 
 }  // namespace rspl

@@ -972,7 +972,7 @@ extern "C" int rspl_lines_extract_wait_device(rspl_lines* h, double* d_lines, in
     h->pin_cap = capacity;
   }
   const int k = h->pin_next;
-  if (!h->copy_ev[k]) RSPL_HIP(hipEventCreateWithFlags(&h->copy_ev[k], hipEventDisableTiming));
+  if (!h->copy_ev[k]) RSPL_HIP(hipEventCreateWithFlags(&h->copy_ev[k], kOrderEventFlags));
   if (h->copy_pending[k]) {  // this slot's copy S joins ago
     RSPL_HIP(hipEventSynchronize(h->copy_ev[k]));
     h->copy_pending[k] = false;
@@ -1053,7 +1053,7 @@ int fld_reserve(rspl_lines* h, size_t hp) {
       set_error("detector scratch carving failed");
       return RSPL_E_DEVICE;
     }
-    for (hipEvent_t& e : h->fld_ev) RSPL_HIP(hipEventCreate(&e));
+    for (hipEvent_t& e : h->fld_ev) RSPL_HIP(hipEventCreateWithFlags(&e, kTimingEventFlags));
   }
   if (hp > h->fld_hp) {
     if (h->fld_img) {
@@ -1328,8 +1328,8 @@ extern "C" int rspl_lines_extract_async_device(rspl_lines* h, const uint8_t* d_i
   constexpr size_t kPinBytes = sizeof(int32_t) * (fld::kMetaInts + 1) + sizeof(float) * 4 * rspl_lines::kDevSegCap;
   if (!h->dev_pin) {
     RSPL_HIP(hipHostMalloc((void**)&h->dev_pin, kPinBytes, hipHostMallocDefault));
-    RSPL_HIP(hipEventCreateWithFlags(&h->dev_in, hipEventDisableTiming));
-    RSPL_HIP(hipEventCreateWithFlags(&h->dev_done, hipEventDisableTiming));
+    RSPL_HIP(hipEventCreateWithFlags(&h->dev_in, kOrderEventFlags));
+    RSPL_HIP(hipEventCreateWithFlags(&h->dev_done, kHostEventFlags));  // the worker reads dev_pin after it
   }
   if (int rc = fld_reserve(h, (size_t)(H / 2) * (W / 2))) return rc;  // the job's device segments live there
   RSPL_HIP(hipEventRecord(h->dev_in, (hipStream_t)stream));

@@ -68,7 +68,20 @@ int rspl_memset(void* dst, int value, size_t bytes, void* stream) {
 }
 int rspl_memcpy_d2d(void* dst, const void* src, size_t bytes, void* stream) {
   if (!bytes) return RSPL_OK;
-  RSPL_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  // both buffers on the current device: the copy kernel (a runtime copy costs more than the launch, and
+  // ends in a system-scope release); a peer's buffer goes through the runtime
+  int cur = -1;
+  hipPointerAttribute_t ad{}, as{};
+  const bool local = hipGetDevice(&cur) == hipSuccess &&
+                     hipPointerGetAttributes(&ad, dst) == hipSuccess && hipPointerGetAttributes(&as, src) == hipSuccess &&
+                     ad.type == hipMemoryTypeDevice && as.type == hipMemoryTypeDevice && ad.device == cur &&
+                     as.device == cur;
+  if (!local) {
+    (void)hipGetLastError();  // (a pointer the runtime does not know: let the copy itself report it)
+    RSPL_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return RSPL_OK;
+  }
+  RSPL_HIP(copy_device(dst, src, bytes, (hipStream_t)stream));
   return RSPL_OK;
 }
 int rspl_stream_create(void** stream) {
@@ -106,7 +119,7 @@ int rspl_stream_synchronize(void* stream) {
 }
 int rspl_event_create(void** event) {
   RSPL_CHECK_ARG(event, "NULL event");
-  RSPL_HIP(hipEventCreateWithFlags((hipEvent_t*)event, hipEventDisableTiming));
+  RSPL_HIP(hipEventCreateWithFlags((hipEvent_t*)event, kOrderEventFlags));  // stream-to-stream ordering only
   return RSPL_OK;
 }
 int rspl_event_record(void* event, void* stream) {
@@ -128,7 +141,8 @@ int rspl_device_synchronize(void) {
 int rspl_timer_create(rspl_timer** t) {
   RSPL_CHECK_ARG(t, "NULL timer");
   auto* x = new rspl_timer();
-  if (hipEventCreate(&x->ev[0]) != hipSuccess || hipEventCreate(&x->ev[1]) != hipSuccess) {
+  if (hipEventCreateWithFlags(&x->ev[0], kTimingEventFlags) != hipSuccess ||
+      hipEventCreateWithFlags(&x->ev[1], kTimingEventFlags) != hipSuccess) {
     set_error("hipEventCreate failed");
     delete x;
     return RSPL_E_DEVICE;

@@ -354,10 +354,10 @@ extern "C" int rspl_sg_create(const rspl_sg_config* cfg, const char* weights_pat
   }
   const size_t nm = s->nmax;
   if (s->timer.init(RSPL_SG_STAGES) != RSPL_OK || hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_ready, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_sink[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_sink[1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_ready, kOrderEventFlags) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_sink[0], kOrderEventFlags) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_sink[1], kOrderEventFlags) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_done, kOrderEventFlags) != hipSuccess ||
       hipHostMalloc(&s->h_f, sizeof(double) * nm * 259 * 2) != hipSuccess ||
       hipHostMalloc(&s->h_idx, sizeof(int32_t) * nm * 2 + 16) != hipSuccess ||
       hipHostMalloc(&s->h_ms, sizeof(double) * nm * 2) != hipSuccess ||
