@@ -795,8 +795,10 @@ int rspl_lines_extract_async_device(rspl_lines* h, const uint8_t* d_image, int H
  * hysteresis kernel -> edge bytes (0 / 255) after the corner zeroing.  _chains: a host edge map through the
  * label and walk kernels -> the chains sorted by seed: seeds [n] (pixel index), offsets [n + 1], points
  * [offsets[n]][2] (x, y); *n_chains is set even when a capacity is exceeded (RSPL_E_CAPACITY).
- * _fld_host: the device code's shared arithmetic on the CPU, with no device: a sequential walk of `edges`,
+ * _fld_host: the host detector from an edge map, with no handle and no device: a sequential walk of `edges`,
  * then fit, filters and orientation against `half` -> segments as rspl_lines_detect orders them.
+ * _fld_classes: the whole host half of rspl_lines_detect, likewise: a class map [hh][hw] through hysteresis and
+ * the corner zeroing, then as _fld_host; *n_out is the count also when it exceeds `capacity`.
  * _fld_stats: image b's counters of the last device detection: edge pixels, components, chains, segments,
  * hysteresis passes, largest component, the walk's iteration count (its busiest lane), status.
  * _fld_profile / _fld_stage_ms: with profiling on, events around the stages of each rspl_lines_detect_device;
@@ -806,6 +808,8 @@ int rspl_lines_debug_chains(rspl_lines* h, const uint8_t* edges, int hh, int hw,
                             int32_t* points, int cap_chains, int cap_points, int* n_chains);
 int rspl_lines_debug_fld_host(const uint8_t* half, const uint8_t* edges, int hh, int hw, const rspl_fld_config* cfg,
                               float* segments, int capacity, int* n_out);
+int rspl_lines_debug_fld_classes(const uint8_t* half, const uint8_t* cls, int hh, int hw, const rspl_fld_config* cfg,
+                                 float* segments, int capacity, int* n_out);
 int rspl_lines_debug_fld_stats(rspl_lines* h, int b, int32_t* stats);
 int rspl_lines_debug_fld_profile(rspl_lines* h, int enable);
 int rspl_lines_debug_fld_stage_ms(rspl_lines* h, float* ms);

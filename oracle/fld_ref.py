@@ -7,7 +7,7 @@ LineDetector::LineExtractor's first two steps (src/line_processor.cc:455-470):
 
 with the configs' parameters (configs/configs_euroc.yaml:31-35: 10, 1.414213562, 200, 250, 3).  It is
 the checker of librspl's rspl_lines_detect (csrc/line_kernels.hip resize + Sobel + Canny
-classification on the GPU, csrc/lines.cpp hysteresis + chaining + segment fitting on the host),
+classification on the GPU, csrc/fld_host.hpp hysteresis + chaining + segment fitting on the host),
 never called by it.
 
 OpenCV (core imgproc + contrib ximgproc) is a third-party dependency that is NOT vendored in the

@@ -1,6 +1,6 @@
 """ORACLE (test infrastructure only): a plain-Python restatement of the reference's line front end
 after the detector -- the LineDetector merge passes, the point-to-line assignment and the
-shared-point line matching -- used to check librspl's csrc/lines.cpp and csrc/line_kernels.hip
+shared-point line matching -- used to check librspl's csrc/line_merge.cpp, csrc/lines.cpp and csrc/line_kernels.hip
 (the product), never called by them.
 
 Restated from (file:line of /root/reference):

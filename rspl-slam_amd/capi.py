@@ -51,6 +51,7 @@ EXPORTS = [
     "rspl_lines_debug_canny",
     "rspl_lines_detect_device", "rspl_lines_detect_status", "rspl_lines_extract_async_device",
     "rspl_lines_debug_hysteresis", "rspl_lines_debug_chains", "rspl_lines_debug_fld_host",
+    "rspl_lines_debug_fld_classes",
     "rspl_lines_debug_fld_stats", "rspl_lines_debug_fld_profile", "rspl_lines_debug_fld_stage_ms",
     "rspl_track_create", "rspl_track_destroy", "rspl_track_set_keyframe", "rspl_track_enqueue", "rspl_track_fetch",
     "rspl_track_debug_stage", "rspl_track_keyframe_table",

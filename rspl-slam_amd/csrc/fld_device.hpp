@@ -1,9 +1,11 @@
 #pragma once
-// The line detector's per-pixel and per-chain arithmetic (FastLineDetector after Canny's classes, restated as
-// oracle/fld_ref.py), one text for the device kernels (fld_kernels.hip) and for the CPU (rspl_lines_debug_fld_host):
-// getPointChain's step, the line through two points, cv::fitLine DIST_L2 from running sums, extractSegments, the
-// float cast with the length and border filters, and the brighter-side-left orientation.  Types and operation
-// order follow fld_from_classes (lines.cpp); FP contraction is off in every function.
+// The line detector's per-pixel and per-chain arithmetic: FastLineDetector after Canny's classes, restating
+// oracle/fld_ref.py.  This header is the text: the device kernels (fld_kernels.hip) and the host detector
+// (fld_host.hpp, behind rspl_lines_detect and the two rspl_lines_debug_fld_* hooks) both compile it, and no rule
+// below is written anywhere else under csrc.  It holds getPointChain's step, the line through two points,
+// cv::fitLine DIST_L2 from running sums, extractSegments, the float cast with the length and border filters, and
+// the brighter-side-left orientation.  Double / float types and operation order are the restatement's, with FP
+// contraction off in every function, so both sides equal it bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -54,28 +56,57 @@ __host__ __device__ inline unsigned neighbour_mask(const Edge& edge, int h, int 
   return nb;
 }
 
-// the neighbour getPointChain takes for a mask, or -1: a function of (mask, direction, step == 0) alone, which
-// the walk kernel tabulates in LDS once per launch
-__host__ __device__ inline int chain_pick(unsigned nb, int direction, int step) {
-#pragma clang fp contract(off)
+// the direction-consistency rule of the later steps: the edge neighbours are offered in index order, the
+// difference to the chain's direction wraps at 4, `<=` gives a tie to the later index, and the winner is taken
+// if it is within 2
+struct Pick {
   float best = 7.0f;
-  int bi = -1;
-  for (int i = 0; i < 8; i++) {
-    if (!((nb >> i) & 1u)) continue;
-    if (step == 0) return i;
-    float diff = fabsf((float)nb_dir(i) - (float)direction);
+  int i = -1;
+  __host__ __device__ void offer(int k, int direction) {
+#pragma clang fp contract(off)
+    float diff = fabsf((float)nb_dir(k) - (float)direction);
     diff = diff > 4.0f ? 8.0f - diff : diff;
     if (diff <= best) {
       best = diff;
-      bi = i;
+      i = k;
     }
   }
-  return bi >= 0 && best < 2.0f ? bi : -1;
+  __host__ __device__ void first(int k) {  // step 0: the first edge neighbour, whatever its direction
+    best = 0.0f;
+    i = k;
+  }
+  __host__ __device__ int taken() const { return i >= 0 && best < 2.0f ? i : -1; }
+};
+
+// the neighbour getPointChain takes for a mask, or -1: a function of (mask, direction, step == 0) alone, which
+// the walk kernel tabulates in LDS once per launch
+__host__ __device__ inline int chain_pick(unsigned nb, int direction, int step) {
+  Pick p;
+  for (int i = 0; i < 8; i++) {
+    if (!((nb >> i) & 1u)) continue;
+    if (step == 0) return i;  // Pick::first, spelt out: the kernels' code stays what it was
+    p.offer(i, direction);
+  }
+  return p.taken();
 }
 
+// one step of a sequential walk (the host detector): tests and rule fused in one loop, which skips a neighbour
+// outside the image or not an edge and leaves at the first one at step 0.  Always inlined: it runs once per edge
+// pixel, and as a call from the walk's loop it costs the host detector 5 to 10 % (measured: DESIGN.md).
 template <class Edge>
-__host__ __device__ inline bool chain_step(const Edge& edge, int h, int w, int& x, int& y, int& direction, int step) {
-  const int i = chain_pick(neighbour_mask(edge, h, w, x, y), direction, step);
+__host__ __device__ inline __attribute__((always_inline)) bool chain_step(const Edge& edge, int h, int w, int& x,
+                                                                          int& y, int& direction, int step) {
+  Pick p;
+  for (int k = 0; k < 8; k++) {
+    const int ci = x + nb_dc(k), ri = y + nb_dr(k);
+    if (ri < 0 || ri == h || ci < 0 || ci == w || !edge(ci, ri)) continue;
+    if (step == 0) {
+      p.first(k);
+      break;
+    }
+    p.offer(k, direction);
+  }
+  const int i = p.taken();
   if (i < 0) return false;
   x += nb_dc(i);
   y += nb_dr(i);

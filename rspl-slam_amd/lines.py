@@ -69,6 +69,7 @@ def _declare(lib):
     lib.rspl_lines_debug_hysteresis.argtypes = [vp, _u8p, ip, ip, _u8p]
     lib.rspl_lines_debug_chains.argtypes = [vp, _u8p, ip, ip, _i32p, _i32p, _i32p, ip, ip, C.POINTER(ip)]
     lib.rspl_lines_debug_fld_host.argtypes = [_u8p, _u8p, ip, ip, C.POINTER(FldConfig), _fp, ip, C.POINTER(ip)]
+    lib.rspl_lines_debug_fld_classes.argtypes = [_u8p, _u8p, ip, ip, C.POINTER(FldConfig), _fp, ip, C.POINTER(ip)]
     lib.rspl_lines_debug_fld_stats.argtypes = [vp, ip, _i32p]
     lib.rspl_lines_debug_fld_profile.argtypes = [vp, ip]
     lib.rspl_lines_debug_fld_stage_ms.argtypes = [vp, _fp]
@@ -132,22 +133,33 @@ def _stream(s):
     return s.handle if isinstance(s, capi.Stream) else s
 
 
-def debug_fld_host(half: np.ndarray, edges: np.ndarray, length_threshold=10, distance_threshold=1.414213562,
-                   capacity: int = 16384) -> np.ndarray:
-    """rspl_lines_debug_fld_host: the device detector's shared arithmetic on the CPU (no device needed): a
-    sequential walk of the edge map `edges` (after hysteresis and corner zeroing), then fit, filters and
-    orientation against the half image -> segments [n][4] float32"""
+def _debug_fld(name, half, pixels, length_threshold, distance_threshold, capacity):
     lib = _declare(capi.load())
     half = np.ascontiguousarray(half, np.uint8)
-    edges = np.ascontiguousarray(edges, np.uint8)
-    assert half.shape == edges.shape and half.ndim == 2
+    pixels = np.ascontiguousarray(pixels, np.uint8)
+    assert half.shape == pixels.shape and half.ndim == 2
     cfg = FldConfig(length_threshold, distance_threshold, 0.0, 0.0, 3)
     seg = np.zeros((max(1, capacity), 4), np.float32)
     n = C.c_int()
-    capi.check(lib.rspl_lines_debug_fld_host(half.ctypes.data_as(_u8p), edges.ctypes.data_as(_u8p), half.shape[0],
-                                             half.shape[1], C.byref(cfg), seg.ctypes.data_as(_fp), capacity,
-                                             C.byref(n)), "rspl_lines_debug_fld_host")
+    capi.check(getattr(lib, name)(half.ctypes.data_as(_u8p), pixels.ctypes.data_as(_u8p), half.shape[0],
+                                  half.shape[1], C.byref(cfg), seg.ctypes.data_as(_fp), capacity, C.byref(n)), name)
     return seg[: n.value].copy()
+
+
+def debug_fld_host(half: np.ndarray, edges: np.ndarray, length_threshold=10, distance_threshold=1.414213562,
+                   capacity: int = 16384) -> np.ndarray:
+    """rspl_lines_debug_fld_host: the host detector from an edge map, with no device: a sequential walk of
+    `edges` (after hysteresis and corner zeroing), then fit, filters and orientation against the half image
+    -> segments [n][4] float32"""
+    return _debug_fld("rspl_lines_debug_fld_host", half, edges, length_threshold, distance_threshold, capacity)
+
+
+def debug_fld_classes(half: np.ndarray, cls: np.ndarray, length_threshold=10, distance_threshold=1.414213562,
+                      capacity: int = 16384) -> np.ndarray:
+    """rspl_lines_debug_fld_classes: the host half of rspl_lines_detect, with no device: Canny classes `cls`
+    (2 strong, 0 candidate, 1 none) through hysteresis and the corner zeroing, then as debug_fld_host
+    -> segments [n][4] float32"""
+    return _debug_fld("rspl_lines_debug_fld_classes", half, cls, length_threshold, distance_threshold, capacity)
 
 
 class LineMatcher:

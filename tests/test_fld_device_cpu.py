@@ -1,11 +1,14 @@
 """The device line detector's CPU-checkable parts (no GPU): the component-wise decomposition restated in Python
 (tests/fld_parallel_ref.py) against oracle/fld_ref.py, the shared host / device header (csrc/fld_device.hpp)
-through rspl_lines_debug_fld_host against the same restatement, bit for bit, and the argument errors of
-rspl_lines_detect_device, refused before a device is touched."""
+through rspl_lines_debug_fld_host against the same restatement, bit for bit, the host detector from Canny's
+classes (csrc/fld_host.hpp, what rspl_lines_detect runs after the Canny kernel) through
+rspl_lines_debug_fld_classes likewise, and the argument errors of rspl_lines_detect_device, refused before a
+device is touched."""
 import ctypes as C
 import functools
 import pathlib
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -20,7 +23,8 @@ from rspl_slam_amd import synthetic as SY
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 IMAGES = [(64, 96, 4, 7), (96, 128, 3, 11), (70, 138, 2, 11)]  # h, w, seed, segments of the sequential detector
 FUNCS = ("rspl_lines_detect_device", "rspl_lines_detect_status", "rspl_lines_extract_async_device",
-         "rspl_lines_debug_hysteresis", "rspl_lines_debug_chains", "rspl_lines_debug_fld_host")
+         "rspl_lines_debug_hysteresis", "rspl_lines_debug_chains", "rspl_lines_debug_fld_host",
+         "rspl_lines_debug_fld_classes")
 
 
 @functools.lru_cache(maxsize=None)
@@ -52,6 +56,99 @@ def test_shared_header_capacity_and_bad_arguments():
         L.debug_fld_host(half, PR.edges_of(half), capacity=3)
     with pytest.raises(capi.RsplError):
         L.debug_fld_host(half, PR.edges_of(half), length_threshold=0)
+
+
+# --- the product's host half from Canny's classes (rspl_lines_debug_fld_classes runs what rspl_lines_detect runs) ---
+DT = 1.414213562
+
+
+def _restate(half, cls, lt=10, dt=DT):
+    chains = PR.walk_sequential(PR.zero_corners(FR.hysteresis(cls).copy()))
+    return np.array([s[2] for s in PR.segments_of(half, chains, lt, dt)], np.float32).reshape(-1, 4)
+
+
+def _random_half(h, w, seed):
+    return np.random.default_rng(seed).integers(0, 256, (h, w)).astype(np.uint8)
+
+
+@pytest.mark.parametrize("h,w,seed,count", IMAGES)
+def test_host_detector_from_classes_equals_the_oracle(h, w, seed, count):
+    half, ref = _case(h, w, seed)
+    got = L.debug_fld_classes(half, FR.canny_classes(half, 200, 250))
+    assert got.dtype == np.float32 and len(got) == count
+    np.testing.assert_array_equal(got, ref)
+
+
+def test_host_detector_spiral_deep_hysteresis_one_long_turning_chain():
+    cls, path = PR.spiral_classes(64)
+    cls[path[len(path) // 2]] = 2
+    half = _random_half(64, 64, 3)
+    ref = _restate(half, cls)
+    assert len(ref) >= 1
+    np.testing.assert_array_equal(L.debug_fld_classes(half, cls), ref)
+
+
+def _box_classes():
+    cls = np.ones((24, 40), np.uint8)
+    cls[7, 7:33] = cls[16, 7:33] = 0
+    cls[7:17, 7] = cls[7:17, 32] = 0
+    cls[7, 20] = 2
+    return cls
+
+
+@pytest.mark.parametrize("lt,count", [(3, 4), (10, 2)])
+def test_host_detector_box_at_two_length_thresholds(lt, count):
+    cls, half = _box_classes(), _random_half(24, 40, 5)
+    ref = _restate(half, cls, lt)
+    assert len(ref) == count
+    np.testing.assert_array_equal(L.debug_fld_classes(half, cls, length_threshold=lt), ref)
+
+
+@pytest.mark.parametrize("lt", [1, 3, 5])
+def test_host_detector_border_ring_gives_no_segment(lt):
+    """both corner zeroings and the border filter apply; the walk tests out-of-image neighbours on all four sides"""
+    cls = np.ones((12, 12), np.uint8)
+    cls[0, :] = cls[-1, :] = cls[:, 0] = cls[:, -1] = 0
+    cls[0, 7] = 2
+    half = _random_half(12, 12, 6)
+    ref = _restate(half, cls, lt)
+    assert len(ref) == 0
+    np.testing.assert_array_equal(L.debug_fld_classes(half, cls, length_threshold=lt), ref)
+
+
+def test_host_detector_two_by_two_of_strong_pixels():
+    got = L.debug_fld_classes(_random_half(2, 2, 7), np.full((2, 2), 2, np.uint8))
+    assert got.shape == (0, 4)  # rc 0: the binding raises on any other
+
+
+def test_host_detector_capacity_and_bad_arguments():
+    half, _ = _case(*IMAGES[1][:3])
+    cls = FR.canny_classes(half, 200, 250)
+    with pytest.raises(capi.RsplError, match="exceed capacity"):
+        L.debug_fld_classes(half, cls, capacity=3)
+    # the rows written before the error, read through the C call itself; a fourth row must stay untouched
+    lib, seg, n = L._declare(capi.load()), np.full((4, 4), -1.0, np.float32), C.c_int()
+    rc = lib.rspl_lines_debug_fld_classes(half.ctypes.data_as(L._u8p), cls.ctypes.data_as(L._u8p), half.shape[0],
+                                          half.shape[1], C.byref(L.FldConfig(10, DT, 0.0, 0.0, 3)),
+                                          seg.ctypes.data_as(L._fp), 3, C.byref(n))
+    ref = _restate(half, cls)
+    assert rc != 0 and n.value == len(ref) > 3
+    np.testing.assert_array_equal(seg[:3], ref[:3])
+    assert (seg[3] == -1.0).all()
+    with pytest.raises(capi.RsplError):
+        L.debug_fld_classes(half, cls, length_threshold=0)
+
+
+def test_host_detector_header_alone_in_a_plain_program():
+    """tests/c/fld_check.cpp: csrc/fld_host.hpp compiled by the host compiler with no librspl, on the box, ring,
+    spiral and 2 x 2 maps built in C++, at capacity 0 and ample; it exits non-zero on any count but the ones above"""
+    exe = ROOT / "tests" / "c" / "build" / "fld_check"
+    # always through make, whose rule names the two headers: a binary of an older header is rebuilt
+    subprocess.run(["make", "-C", str(ROOT / "tests" / "c"), "build/fld_check"], check=True, capture_output=True)
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0 and "FAILED" not in run.stdout, run.stdout + run.stderr
+    for name in ("box", "ring", "spiral", "2x2"):
+        assert any(line.startswith(name) for line in run.stdout.splitlines()), run.stdout
 
 
 def test_header_and_binding_declare_the_device_detector():

@@ -1,6 +1,6 @@
 """Line front end after the detector, CPU part.
 
-librspl's LineDetector post-processing (rspl_line_extract, host C++: csrc/lines.cpp) against the
+librspl's LineDetector post-processing (rspl_line_extract, host C++: csrc/line_merge.cpp) against the
 oracle's restatement (oracle/lines_ref.py) of LineDetector::LineExtractor / MergeLines /
 MergeTwoLines / FilterShortLines (src/line_processor.cc:11-161, 460-665): bit-exact lines on
 synthetic FLD-like fragment sets.  The oracle's assignment / matching restatements are checked on
