@@ -101,7 +101,8 @@ void rspl_timer_destroy(rspl_timer* t);
 /* kMAX does (src/super_point.cpp:46-53).                                 */
 /* ------------------------------------------------------------------------ */
 typedef struct {
-  int max_keypoints;         /* top-k; -1 keeps all (top_k_keypoints, src/super_point.cpp:192-204) */
+  int max_keypoints;         /* top-k; -1 keeps all, 0 yields no keypoints (top_k_keypoints, src/super_point.cpp:192-204);
+                              * below -1 or above 16384 is RSPL_E_ARG */
   double keypoint_threshold; /* scores > threshold (src/super_point.cpp:154-165) */
   int remove_borders;        /* border in pixels (src/super_point.cpp:168-183) */
   int max_height;            /* arena sizing; H, W must be multiples of 8 */
@@ -137,6 +138,20 @@ int rspl_sp_debug_maps(rspl_sp* sp, int b, float* scores, float* desc);
 /* Test hook: the device simple_nms (convert2onnx/superpoint.py:6-33, radius 4) of a host
  * score map [H][W] (any H, W within the arena) -> out [H][W]. */
 int rspl_sp_debug_nms(rspl_sp* sp, const float* scores, int height, int width, float* out);
+
+/* Test hook (RSPL_PREC_FP32 handles; otherwise RSPL_E_ARG): the tail every precision shares -- NMS with candidate
+ * extraction, top-k and the fp32 descriptor sampler -- on host maps, through the same function and argument
+ * construction as rspl_sp_infer_device, with the handle's own max_keypoints, keypoint_threshold and remove_borders.
+ *   scores    f32 [B][H][W]              dense pre-NMS score maps, as the detector head leaves them
+ *   desc      f32 [B][(H/8)*(W/8)][256]  dense descriptor maps in the device layout (cell-major)
+ *   features  f64 [B][capacity][259]     in/out: uploaded as it stands (a test may prefill it), then downloaded;
+ *                                        capacity = max_keypoints (16384 for -1, 1 for 0)
+ *   counts [B] keypoints per image, cand_counts [B] the per-image candidate counter after NMS.
+ * H, W multiples of 8 within the arena.  Keep-all (max_keypoints = -1) with more than 16384 candidates gives count 0
+ * here exactly as rspl_sp_infer_device does, silently: only rspl_sp_infer reports it (RSPL_E_CAPACITY); cand_counts
+ * shows it. */
+int rspl_sp_debug_select(rspl_sp* sp, const float* scores, const float* desc, int batch, int height, int width,
+                         double* features, int capacity, int32_t* counts, int32_t* cand_counts);
 
 /* Test hook (RSPL_PREC_FP16 handles; otherwise RSPL_E_ARG): run ONE fp16 stage of the handle on host input,
  * through the same launcher call with the same arguments as rspl_sp_infer_device, and copy its output back.

@@ -52,7 +52,8 @@ class SuperPoint:
         return rc == 0
 
     def _cap(self):
-        return self.config.max_keypoints if self.config.max_keypoints > 0 else 16384
+        k = self.config.max_keypoints  # -1 keeps all (up to 16384); 0 yields none (one slot, never written)
+        return 16384 if k == -1 else max(k, 1)
 
     def infer(self, image: np.ndarray) -> Tuple[bool, np.ndarray]:
         """SuperPoint::infer (src/super_point.cpp:104-135): u8 [H, W] -> (ok, features [259, N])."""
@@ -132,6 +133,24 @@ class SuperPoint:
                                                  cnt.ctypes.data, stride, out.ctypes.data, cout.ctypes.data),
                    "rspl_sp_debug_layer")
         return [out[b, :cout[b]].copy() for b in range(B)], cout
+
+    def debug_select(self, scores: np.ndarray, desc: np.ndarray, fill: float = 0.0):
+        """rspl_sp_debug_select: NMS + candidates, top-k and the fp32 sampler of an RSPL_PREC_FP32 handle on host maps,
+        launched as rspl_sp_infer_device launches them.  scores [B, H, W] pre-NMS; desc [B, 256, H/8, W/8]
+        (channel-major like the reference tensor; transposed here to the device's cell-major layout).  Every feature
+        slot is prefilled with `fill`.  Returns (features [B, capacity, 259] float64 as downloaded, counts [B],
+        cand_counts [B])."""
+        sc = np.ascontiguousarray(scores, np.float32)
+        B, H, W = sc.shape
+        d = np.asarray(desc, np.float32)
+        assert d.shape == (B, 256, H // 8, W // 8), d.shape
+        d = np.ascontiguousarray(d.reshape(B, 256, -1).transpose(0, 2, 1))
+        cap = self._cap()
+        F = np.full((B, cap, 259), fill, np.float64)
+        cnt, cand = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        capi.check(self._lib.rspl_sp_debug_select(self._h, sc.ctypes.data, d.ctypes.data, B, H, W, F.ctypes.data, cap,
+                                                  cnt.ctypes.data, cand.ctypes.data), "rspl_sp_debug_select")
+        return F, cnt, cand
 
     def debug_maps(self, b: int, height: int, width: int):
         s = np.empty((height, width), np.float32)

@@ -31,6 +31,7 @@ EXPORTS = [
     "rspl_event_destroy", "rspl_timer_create", "rspl_timer_record", "rspl_timer_elapsed_ms",
     "rspl_timer_destroy",
     "rspl_sp_create", "rspl_sp_infer", "rspl_sp_infer_device", "rspl_sp_debug_maps", "rspl_sp_debug_nms", "rspl_sp_debug_layer",
+    "rspl_sp_debug_select",
     "rspl_sp_profile",
     "rspl_sp_stage_times", "rspl_sp_destroy",
     "rspl_sg_create", "rspl_sg_infer", "rspl_sg_infer_device", "rspl_sg_infer_device2", "rspl_sg_debug_scores", "rspl_sg_profile",
@@ -254,6 +255,7 @@ def load(path: pathlib.Path = LIB_PATH):
     lib.rspl_sp_debug_maps.argtypes = [vp, ip, vp, vp]
     lib.rspl_sp_debug_nms.argtypes = [vp, vp, ip, ip, vp]
     lib.rspl_sp_debug_layer.argtypes = [vp, ip, ip, ip, ip, vp, vp, vp, vp, ip, vp, vp]
+    lib.rspl_sp_debug_select.argtypes = [vp, vp, vp, ip, ip, ip, vp, ip, vp, vp]
     lib.rspl_sp_destroy.argtypes = [vp]
     lib.rspl_sp_destroy.restype = None
     lib.rspl_device_count.argtypes = [C.POINTER(ip)]

@@ -14,6 +14,10 @@ using namespace rspl;
 static constexpr int kCandCap = 16384;  // candidates sorted whole in LDS (bitonic top-k); also the keep-all and
                                         // max_keypoints limits.  More candidates (large images) are radix-selected.
 
+// Feature slots per image for max_keypoints = k: -1 keeps all (up to kCandCap), 0 yields none (one slot, never
+// written: the samplers launch per slot and their first block of an image writes its count)
+static int keypoint_slots(int k) { return k == -1 ? kCandCap : std::max(k, 1); }
+
 struct rspl_sp {
   rspl_sp_config cfg{};
   hipStream_t stream = nullptr;
@@ -122,7 +126,8 @@ extern "C" int rspl_sp_create(const rspl_sp_config* cfg, const char* weights_pat
                      cfg->precision == RSPL_PREC_FP16X3,
                  "precision must be RSPL_PREC_FP32, RSPL_PREC_FP16 or RSPL_PREC_FP16X3");
   RSPL_CHECK_ARG(cfg->remove_borders >= 0, "remove_borders must be >= 0");
-  RSPL_CHECK_ARG(cfg->max_keypoints <= kCandCap, "max_keypoints must be <= %d", kCandCap);
+  RSPL_CHECK_ARG(cfg->max_keypoints >= -1 && cfg->max_keypoints <= kCandCap,
+                 "max_keypoints must be -1 (keep all) or within [0, %d]", kCandCap);
   *out = nullptr;
   std::vector<Tensor> ts;
   int rc = load_blob(weights_path, ts);
@@ -132,7 +137,7 @@ extern "C" int rspl_sp_create(const rspl_sp_config* cfg, const char* weights_pat
   s->cfg = *cfg;
   if (s->cfg.max_batch < 1) s->cfg.max_batch = 1;
   const int B = s->cfg.max_batch, H = cfg->max_height, W = cfg->max_width;
-  s->feat_cap = cfg->max_keypoints > 0 ? cfg->max_keypoints : kCandCap;
+  s->feat_cap = keypoint_slots(cfg->max_keypoints);
   // one slot per pixel: the candidate buffer cannot overflow whatever survives simple_nms
   // (flat plateaus keep every tied pixel), so no device path ever truncates it
   s->cand_cap = std::max(kCandCap, H * W);
@@ -316,10 +321,33 @@ sp::TapArgs h16_taps(const rspl_sp* s, int prec, double* d_features, int capacit
   const int k = s->cfg.max_keypoints;
   sp::TapArgs ta{};
   ta.cells = as_half(s->cells); ta.wDb = s->fwDb; ta.bDb = s->bDb;
-  ta.sel = s->sel; ta.sel_count = s->sel_count; ta.sel_stride = kCandCap; ta.per_image = (k > 0 ? k : kCandCap);
+  ta.sel = s->sel; ta.sel_count = s->sel_count; ta.sel_stride = kCandCap; ta.per_image = keypoint_slots(k);
   ta.nms = s->scores; ta.features = d_features; ta.feat_cap = capacity; ta.counts = d_counts; ta.B = B; ta.H = H; ta.W = W;
   if (prec == RSPL_PREC_FP16X3) { ta.cells_lo = ta.cells + (size_t)B * (H / 8) * (W / 8) * 512; ta.wDb_lo = s->lfwDb; }
   return ta;
+}
+
+// The tail every precision shares, from the dense score map in s->scores (and, fp32, the dense descriptors in
+// s->desc) to the packed feature records: NMS + candidates, top-k, descriptor sampling, with stage marks 5, 6, 7.
+// One function for rspl_sp_infer_device and rspl_sp_debug_select, so that the test hook launches what the
+// product launches.
+int select_and_sample(rspl_sp* s, int B, int H, int W, double* d_features, int capacity, int32_t* d_counts,
+                      hipStream_t st) {
+  using namespace sp;
+  const int k = s->cfg.max_keypoints, prec = s->cfg.precision;
+  if (int rc = nms_topk(s, B, H, W, k, st)) return rc;
+  s->timer.mark(6, st);
+  if (prec == RSPL_PREC_FP32) {  // descriptor sampling + packing (super_point.cpp:206-319)
+    SampleArgs sa{};
+    sa.sel = s->sel; sa.sel_count = s->sel_count; sa.sel_stride = kCandCap; sa.per_image = keypoint_slots(k);
+    sa.nms = s->scores; sa.desc = s->desc; sa.features = d_features; sa.feat_cap = capacity;
+    sa.counts = d_counts; sa.B = B; sa.H = H; sa.W = W;
+    RSPL_HIP(sample(sa, st));
+  } else {
+    RSPL_HIP(sample_taps_h(h16_taps(s, prec, d_features, capacity, d_counts, B, H, W), prec == RSPL_PREC_FP16X3, st));
+  }
+  s->timer.mark(7, st);
+  return RSPL_OK;
 }
 }  // namespace
 
@@ -331,8 +359,8 @@ extern "C" int rspl_sp_infer_device(rspl_sp* s, const uint8_t* d_images, int B, 
   RSPL_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && H <= s->cfg.max_height && W <= s->cfg.max_width,
                  "image %dx%d: must be multiples of 8 within %dx%d", H, W, s->cfg.max_height, s->cfg.max_width);
   RSPL_CHECK_ARG(stride >= W, "stride < width");
-  const int k = s->cfg.max_keypoints, prec = s->cfg.precision;
-  RSPL_CHECK_ARG(capacity >= (k > 0 ? k : kCandCap), "capacity %d below max_keypoints", capacity);
+  const int prec = s->cfg.precision;
+  RSPL_CHECK_ARG(capacity >= keypoint_slots(s->cfg.max_keypoints), "capacity %d below max_keypoints", capacity);
   hipStream_t st = stream_ ? (hipStream_t)stream_ : s->stream;
   const int W8 = W / 8, P = (H / 8) * W8;
   using namespace sp;
@@ -361,18 +389,7 @@ extern "C" int rspl_sp_infer_device(rspl_sp* s, const uint8_t* d_images, int B, 
     RSPL_HIP(det_head_h(h16_head(s, prec, B, P, W8), prec == RSPL_PREC_FP16X3, st));
   }
   s->timer.mark(4, st);
-  if (int rc = nms_topk(s, B, H, W, k, st)) return rc;
-  s->timer.mark(6, st);
-  if (prec == RSPL_PREC_FP32) {  // descriptor sampling + packing (super_point.cpp:206-319)
-    SampleArgs sa{};
-    sa.sel = s->sel; sa.sel_count = s->sel_count; sa.sel_stride = kCandCap; sa.per_image = (k > 0 ? k : kCandCap);
-    sa.nms = s->scores; sa.desc = s->desc; sa.features = d_features; sa.feat_cap = capacity;
-    sa.counts = d_counts; sa.B = B; sa.H = H; sa.W = W;
-    RSPL_HIP(sample(sa, st));
-  } else {
-    RSPL_HIP(sample_taps_h(h16_taps(s, prec, d_features, capacity, d_counts, B, H, W), prec == RSPL_PREC_FP16X3, st));
-  }
-  s->timer.mark(7, st);
+  if (int rc = select_and_sample(s, B, H, W, d_features, capacity, d_counts, st)) return rc;
   s->timer.end_call();
   s->last_B = B; s->last_H = H; s->last_W = W;
   return RSPL_OK;
@@ -396,8 +413,8 @@ extern "C" int rspl_sp_infer(rspl_sp* s, const uint8_t* image, int H, int W, int
     set_error("%d candidates above threshold exceed the candidate buffer %d", cand, s->cand_cap);
     return RSPL_E_CAPACITY;
   }
-  if (s->cfg.max_keypoints <= 0 && cand > kCandCap) {
-    set_error("keep-all (max_keypoints <= 0): %d candidates exceed %d", cand, kCandCap);
+  if (s->cfg.max_keypoints == -1 && cand > kCandCap) {
+    set_error("keep-all (max_keypoints == -1): %d candidates exceed %d", cand, kCandCap);
     return RSPL_E_CAPACITY;
   }
   const int n = s->h_counts[0];
@@ -467,6 +484,29 @@ extern "C" int rspl_sp_debug_nms(rspl_sp* s, const float* scores, int H, int W, 
   RSPL_HIP(hipMemcpyAsync(out, s->nms, sizeof(float) * H * W, hipMemcpyDeviceToHost, st));
   RSPL_HIP(hipStreamSynchronize(st));
   s->last_B = 0;
+  return RSPL_OK;
+}
+
+extern "C" int rspl_sp_debug_select(rspl_sp* s, const float* scores, const float* desc, int B, int H, int W,
+                                    double* features, int capacity, int32_t* counts, int32_t* cand_counts) {
+  RSPL_CHECK_ARG(s && scores && desc && features && counts && cand_counts, "rspl_sp_debug_select: NULL argument");
+  RSPL_CHECK_ARG(s->cfg.precision == RSPL_PREC_FP32, "rspl_sp_debug_select: the handle must be RSPL_PREC_FP32");
+  RSPL_CHECK_ARG(B >= 1 && B <= s->cfg.max_batch, "batch %d outside [1, %d]", B, s->cfg.max_batch);
+  RSPL_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && H <= s->cfg.max_height && W <= s->cfg.max_width,
+                 "map %dx%d: must be multiples of 8 within %dx%d", H, W, s->cfg.max_height, s->cfg.max_width);
+  RSPL_CHECK_ARG(capacity == s->feat_cap, "capacity %d: the handle holds %d records per image", capacity, s->feat_cap);
+  hipStream_t st = s->stream;
+  RSPL_HIP(hipStreamSynchronize(st));
+  s->last_B = 0;  // the maps of the last inference are overwritten
+  const size_t HW = (size_t)H * W, nfeat = (size_t)B * capacity * 259;
+  RSPL_HIP(hipMemcpy(s->scores, scores, sizeof(float) * B * HW, hipMemcpyHostToDevice));
+  RSPL_HIP(hipMemcpy(s->desc, desc, sizeof(float) * B * (HW / 64) * 256, hipMemcpyHostToDevice));
+  RSPL_HIP(hipMemcpy(s->features, features, sizeof(double) * nfeat, hipMemcpyHostToDevice));
+  if (int rc = select_and_sample(s, B, H, W, s->features, capacity, s->counts, st)) return rc;
+  RSPL_HIP(hipStreamSynchronize(st));
+  RSPL_HIP(hipMemcpy(features, s->features, sizeof(double) * nfeat, hipMemcpyDeviceToHost));
+  RSPL_HIP(hipMemcpy(counts, s->counts, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+  RSPL_HIP(hipMemcpy(cand_counts, s->cand_count, sizeof(int) * B, hipMemcpyDeviceToHost));
   return RSPL_OK;
 }
 

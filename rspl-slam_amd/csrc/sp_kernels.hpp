@@ -87,7 +87,7 @@ struct TopkArgs {
   const int* cand_count;
   int cand_cap;          // candidate buffer stride per image
   int lds_cap;           // candidates sorted whole in LDS; beyond it (k > 0) radix select first
-  int k;                 // -1 = keep all
+  int k;                 // -1 = keep all, 0 = keep none (count 0), otherwise the k best
   unsigned* sel;         // [B][sel_cap] flat indices
   int* sel_count;        // [B]
   int sel_cap;

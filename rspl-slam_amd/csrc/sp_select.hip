@@ -253,7 +253,9 @@ __global__ __launch_bounds__(1024) void topk_kernel(TopkArgs a) {
   if (n > a.cand_cap) n = a.cand_cap;
   const bool sorted_by_score = (a.k != -1 && a.k < n);
   const unsigned long long* src = a.cand + (size_t)bi * a.cand_cap;
-  if (n > a.lds_cap && !sorted_by_score) {  // keep-all beyond the LDS sort: reported by the host
+  // k = 0 keeps nothing (the reference's k < n sort-and-resize, src/super_point.cpp:192-204): no select, keys[]
+  // untouched.  Keep-all beyond the LDS sort also yields 0, reported by the host.
+  if (a.k == 0 || (n > a.lds_cap && !sorted_by_score)) {
     if (threadIdx.x == 0) a.sel_count[bi] = 0;
     return;
   }
