@@ -1386,6 +1386,149 @@ int rspl_fm_debug_seven_point(const double* p0, const double* p1, double* F, int
  * counts, inlier counts [max][3] and models [max][3][9]; returns how many, or a negative error */
 int rspl_fm_debug_hypotheses(rspl_fm* h, int frame, int max, int32_t* n_models, int32_t* counts, double* F);
 
+/* ------------------------------------------------------------------------ */
+/* Local map tracking: Map::SearchByProjection (src/map.cc:952-1005) and     */
+/* MapBuilder::TrackLocalMap (src/map_builder.cc:753-785) for a batch of     */
+/* independent frames.  The reference never calls this path (DESIGN section  */
+/* 9); it is restated from its text, and parity is with tests/lmap_ref.py.   */
+/*   bank     one fp64 descriptor (256 values) per map point id: the one     */
+/*            Map::InsertKeyframe stores at creation (map.cc:44-47)          */
+/*   local    the ordered local map: ids (resolved to bank rows), positions  */
+/*   search   per local point the frame does not hold: pc = Rwc^T (pw - twc),*/
+/*            Camera::StereoProject, the strict image bounds, the candidates */
+/*            of Frame::FindNeighborKeypoints(r, filter = true), best and    */
+/*            second-best 2 (1 - d_point . d_kp), the 0.35 / 0.6 test.  An   */
+/*            exact tie in the distance goes to the keypoint the reference's */
+/*            64 x 48 grid walk visits first: argmin over (dist, gx, gy, idx)*/
+/*   merge    the ordered good list; per keypoint the frame's own point or   */
+/*            the LAST good projection that claims it (TrackLocalMap's loop) */
+/*   chain    the merged table written into an rspl_track keyframe slot and  */
+/*            rspl_track_enqueue behind it on the same stream                */
+/* The descriptor distance has one summation order everywhere (lane l of 64  */
+/* owns entries 4l..4l+3, ((a0 b0 + a1 b1) + a2 b2) + a3 b3, the 64 partials */
+/* by the xor butterfly 32..1), so the device and rspl_lmap_debug_search_host*/
+/* agree bit for bit.                                                        */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  int max_bank_points;   /* descriptors the bank holds */
+  int max_local_points;  /* local map points per rspl_lmap_set_local */
+  int max_keypoints;     /* keypoints per frame, at most 8192 */
+  int max_batch;
+  int device;            /* < 0: a host-only handle -- bank and local-table bookkeeping with the descriptors kept
+                          * on the host (rspl_lmap_store_host, rspl_lmap_set_local); every device call is refused */
+  double radius;         /* 15 (r = 15 thr, thr = 1) */
+  double max_distance;   /* 0.35 */
+  double max_ratio;      /* 0.6 */
+} rspl_lmap_config;
+
+/* per local point, rspl_lmap_debug_points / rspl_lmap_debug_search_host */
+#define RSPL_LMAP_NOT_SELECTED 0  /* the frame already holds this point */
+#define RSPL_LMAP_BEHIND 1        /* pc.z <= 0 */
+#define RSPL_LMAP_OFF_IMAGE 2     /* not 0 < u < W and 0 < v < H */
+#define RSPL_LMAP_NO_CANDIDATE 3
+#define RSPL_LMAP_FAILED 4        /* best >= max_distance or best >= max_ratio * second */
+#define RSPL_LMAP_GOOD 5
+
+typedef struct {
+  const double* d_features;    /* DEVICE SuperPoint records [cap][259] (x, y = rows 1, 2; descriptor = rows 3..258) */
+  const int32_t* d_n1;         /* DEVICE keypoint count (clamped to max_keypoints) */
+  const double* d_u_right;     /* DEVICE [n1] right-image u, -1 without a stereo partner: the reference's dxr test.
+                                * NULL: the dxr term is skipped (a tracking frame has no right image) */
+  const int32_t* d_point_id;   /* DEVICE [n1] id of the non-bad map point keypoint i holds, or -1 */
+  const double* d_point_xyz;   /* DEVICE [n1][3] its position (read where d_point_id >= 0) */
+  const uint8_t* d_point_good; /* DEVICE [n1] 1: that point is Good (an edge of the pose optimisation), 0: held but
+                                * not Good (RSPL_TRACK_NOT_GOOD in the chained table).  NULL: every held point is Good */
+  double Twc[16];              /* the pose to project with, row-major 4x4 */
+  double fx, fy, cx, cy, bf;
+  int width, height;
+} rspl_lmap_frame;
+
+typedef struct {
+  int n_keypoints;         /* as the device read it */
+  int n_selected;          /* local points the frame does not hold */
+  int n_projected;         /* ... in front of the camera and inside the image */
+  int n_with_candidates;
+  int n_good;
+  /* caller arrays (each may be NULL) */
+  int32_t* good_kp;        /* [max_local_points] the good projections in local-map order: keypoint ... */
+  int32_t* good_point;     /* ... and LOCAL INDEX of the point; the first n_good are written */
+  int32_t* assoc_id;       /* [max_keypoints] the merged table: map point id per keypoint or -1; the first
+                            * n_keypoints are written */
+} rspl_lmap_result;
+
+typedef struct rspl_lmap rspl_lmap;
+
+int rspl_lmap_create(const rspl_lmap_config* cfg, rspl_lmap** out);
+void rspl_lmap_destroy(rspl_lmap* h);
+/* Mappoint::SetDescriptor at creation: rows 3..258 of record keypoints[k] of the DEVICE records d_features become
+ * the descriptor of map point ids[k] (ids, keypoints: host arrays, copied before the call returns; the copy is
+ * stream-ordered on `stream`, NULL: the handle's).  An id the bank already has is overwritten; an id that does
+ * not fit fails with RSPL_E_CAPACITY and stores nothing of the call. */
+int rspl_lmap_store(rspl_lmap* h, int n, const int32_t* ids, const int32_t* keypoints, const double* d_features,
+                    void* stream);
+/* the same from host descriptors [n][256]; returns after the copy */
+int rspl_lmap_store_host(rspl_lmap* h, int n, const int32_t* ids, const double* descriptors);
+int rspl_lmap_bank_size(const rspl_lmap* h, int* n);
+/* The local map, in order: ids[n] and positions[n][3] (host arrays, copied before the call returns; uploaded on
+ * `stream`).  Ids are resolved to bank rows here -- the search reads the bank through that table, no descriptor
+ * is copied.  An id without a descriptor fails with RSPL_E_ARG and rspl_last_error names it; the local map is
+ * then unchanged. */
+int rspl_lmap_set_local(rspl_lmap* h, int n, const int32_t* ids, const double* positions, void* stream);
+/* Search + merge for frames[0 .. batch) against the local map on `stream` (NULL: the handle's).  No host
+ * synchronisation; one enqueue in flight per handle: fetch before the next.  The enqueue's stream waits (on the
+ * device) for the handle's last rspl_lmap_store and rspl_lmap_set_local, whatever streams they went to; what
+ * produces the frame's own device arrays must be ordered before it by the caller. */
+int rspl_lmap_enqueue(rspl_lmap* h, int batch, const rspl_lmap_frame* frames, void* stream);
+/* Wait for the last enqueue; results[b] receives frame b. */
+int rspl_lmap_fetch(rspl_lmap* h, rspl_lmap_result* results);
+/* frame `frame` of the last fetched enqueue, per local point (arrays of the local map's length, each may be NULL):
+ * status RSPL_LMAP_*, best_idx (-1: none), best and second (4.0 where nothing was below it) */
+int rspl_lmap_debug_points(rspl_lmap* h, int frame, int32_t* status, int32_t* best_idx, double* best, double* second);
+/* The chain: search, merge into t's keyframe slots tf[b].slot (through rspl_track_keyframe_table with n0 =
+ * max_keypoints: t's max_keypoints must not be smaller) and rspl_track_enqueue(t, batch, tf, stream) with the
+ * handle's identity indices in place of tf[b].d_idx0 / d_idx1 (both ignored).  Per keypoint j of the slot: the
+ * frame's own point, else the winning projection (state RSPL_TRACK_GOOD, track id = the point's id), else
+ * RSPL_TRACK_NO_MAPPOINT.  Results: rspl_track_fetch and rspl_lmap_fetch.  TrackLocalMap's gates (fewer than 3
+ * good projections; n_inliers > min_num_match && n_inliers > num_inlier_thr) are the caller's, from the fetched
+ * counts: the chain always runs.  As in the tracking step a point whose id is 0 is dropped by `> 0`.  The tracker
+ * is handed the keypoint count the search used (*d_n1 clamped to this handle's max_keypoints), not tf[b].d_n1, so
+ * both fetches report the same n_keypoints.  `t` must live on the handle's device.  When the call fails at frame b's
+ * slot, the slots of frames before b keep the keypoint count max_keypoints that the call gave them. */
+int rspl_lmap_track_enqueue(rspl_lmap* h, rspl_track* t, int batch, const rspl_lmap_frame* frames,
+                            const rspl_track_frame* tf, void* stream);
+
+/* debug (parity tests): the host instantiation of the search text (csrc/lmap_match.hpp) on host arrays */
+typedef struct {
+  int n_keypoints;
+  const double* features;      /* [n_keypoints][259] */
+  const double* u_right;       /* [n_keypoints] or NULL */
+  const int32_t* point_id;     /* [n_keypoints] */
+  int n_local;
+  const int32_t* local_ids;    /* [n_local] */
+  const double* local_pos;     /* [n_local][3] */
+  const double* local_desc;    /* [n_local][256] */
+  double Twc[16];
+  double fx, fy, cx, cy, bf;
+  int width, height;
+  double radius, max_distance, max_ratio;
+} rspl_lmap_host_problem;
+int rspl_lmap_debug_search_host(const rspl_lmap_host_problem* p, int32_t* status, int32_t* best_idx, double* best,
+                                double* second);
+
+/* Local map selection on the native map (MapBuilder::UpdateReferenceFrame, UpdateLocalKeyframes,
+ * UpdateLocalMappoints; src/map_builder.cc:684-734). */
+/* point_ids[n]: the current frame's slots (map point id or -1; bad and unknown ids are skipped, untriangulated
+ * ones count).  Every observer of those points other than current_frame_id that the map knows gets one vote per
+ * point; the reference keyframe becomes the observer with the most votes (strictly; ties: the lowest frame id).
+ * *ref = that frame (current_ref when nobody was counted), *changed = it differs from current_ref. */
+int rspl_map_reference_keyframe(const rspl_map* m, int current_frame_id, int n, const int32_t* point_ids,
+                                int current_ref, int* ref, int* changed);
+/* The Good map points of ref_frame_id's neighbours, GetOrderedConnections(-1) order (ascending weight, frame id;
+ * the reference keyframe itself is not walked), each frame's slots in keypoint order, first occurrence only.
+ * *n = how many there are; ids / positions (each may be NULL) receive them when cap >= *n, otherwise nothing is
+ * written and the call fails with RSPL_E_CAPACITY. */
+int rspl_map_local_mappoints(const rspl_map* m, int ref_frame_id, int32_t* ids, double* positions, int cap, int* n);
+
 
 #ifdef __cplusplus
 }

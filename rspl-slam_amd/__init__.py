@@ -13,7 +13,8 @@ from .rcf import RCF  # noqa: F401
 _API = ("SuperPoint", "SuperPointConfig", "SuperGlue", "SuperGlueConfig", "PointMatching",
         "LocalmapOptimization", "LocalBA", "FrameOptimization", "FrameBA",
         "ShardGroup", "Comm", "comm_unique_id", "broadcast_comm_id", "PnP", "SolvePnPWithCV",
-        "Tracker", "TrackFrame", "KeyframeBuilder", "triangulate_points", "stereo_window", "FundamentalRansac")
+        "Tracker", "TrackFrame", "KeyframeBuilder", "triangulate_points", "stereo_window", "FundamentalRansac",
+        "LocalMap", "TrackLocalMap", "lmap_search_host")
 
 
 def __getattr__(name):

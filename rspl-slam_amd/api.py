@@ -839,17 +839,9 @@ class Tracker:
                                                      tid.ctypes.data, _stream_handle(stream)),
                    "rspl_track_set_keyframe")
 
-    def enqueue(self, frames, stream=None):
-        """frames: list of dicts with the device addresses ``d_features``, ``d_n1``, ``d_idx0``, ``d_idx1``
-        (ints or capi.DeviceBuffer), optional ``d_u_right``, ``slot`` (default 0), ``cam`` = (fx, fy, cx, cy,
-        bf), ``last_Twc`` [4, 4], and optional ``th_mono_point`` / ``th_stereo_point`` (5.991 / 7.815) and
-        ``min_num_match`` (10).
-
-        When any frame carries ``d_lines`` or ``keyframe`` the batch goes through rspl_track_enqueue_ext (after
-        ``enable_lines``): line tracking against the slot's ``set_keyframe_lines`` and the keyframe decision.
-        ``d_lines`` (device [n_lines, 4] doubles) comes with ``n_lines``; ``keyframe`` = dict(Twc [4, 4],
-        frame_id) is the last keyframe, ``frame_id`` this frame's; optional ``max_num_match`` (80),
-        ``max_angle`` (0.52), ``max_distance`` (0.5), ``max_num_passed_frame`` (300)."""
+    @staticmethod
+    def _frame_descs(frames):
+        """rspl_track_frame records of ``enqueue``'s dicts (a missing device address stays NULL)"""
         F = (capi.TrackFrameDesc * max(len(frames), 1))()
         for f, d in zip(F, frames):
             f.slot = d.get("slot", 0)
@@ -861,6 +853,24 @@ class Tracker:
             f.th_mono_point = d.get("th_mono_point", 5.991)
             f.th_stereo_point = d.get("th_stereo_point", 7.815)
             f.min_num_match = d.get("min_num_match", 10)
+        return F
+
+    def _enqueued_by(self, batch):
+        """another handle (LocalMap.track_enqueue) issued rspl_track_enqueue for ``batch`` frames: ``fetch`` is next"""
+        self._batch, self._ext = int(batch), False
+
+    def enqueue(self, frames, stream=None):
+        """frames: list of dicts with the device addresses ``d_features``, ``d_n1``, ``d_idx0``, ``d_idx1``
+        (ints or capi.DeviceBuffer), optional ``d_u_right``, ``slot`` (default 0), ``cam`` = (fx, fy, cx, cy,
+        bf), ``last_Twc`` [4, 4], and optional ``th_mono_point`` / ``th_stereo_point`` (5.991 / 7.815) and
+        ``min_num_match`` (10).
+
+        When any frame carries ``d_lines`` or ``keyframe`` the batch goes through rspl_track_enqueue_ext (after
+        ``enable_lines``): line tracking against the slot's ``set_keyframe_lines`` and the keyframe decision.
+        ``d_lines`` (device [n_lines, 4] doubles) comes with ``n_lines``; ``keyframe`` = dict(Twc [4, 4],
+        frame_id) is the last keyframe, ``frame_id`` this frame's; optional ``max_num_match`` (80),
+        ``max_angle`` (0.52), ``max_distance`` (0.5), ``max_num_passed_frame`` (300)."""
+        F = self._frame_descs(frames)
         self._ext = any("d_lines" in d or "keyframe" in d for d in frames)
         if not self._ext:
             capi.check(self._lib.rspl_track_enqueue(self._h, len(frames), F, _stream_handle(stream)),
@@ -1012,6 +1022,188 @@ class Tracker:
         if getattr(self, "_h", None) and self._h.value:
             self._lib.rspl_track_destroy(self._h)
             self._h = C.c_void_p()
+
+
+# ---------------------------------------------------------------------------
+# Local map tracking: Map::SearchByProjection (src/map.cc:952-1005) and MapBuilder::TrackLocalMap
+# (src/map_builder.cc:753-785) -- dead code in the reference, restated (tests/lmap_ref.py)
+# ---------------------------------------------------------------------------
+LMAP_NOT_SELECTED, LMAP_BEHIND, LMAP_OFF_IMAGE, LMAP_NO_CANDIDATE, LMAP_FAILED, LMAP_GOOD = range(6)  # RSPL_LMAP_*
+
+
+def _lmap_frames(frames):
+    F = (capi.LmapFrame * max(len(frames), 1))()
+    for f, d in zip(F, frames):
+        for k in ("d_features", "d_n1", "d_u_right", "d_point_id", "d_point_xyz", "d_point_good"):
+            v = d.get(k)
+            setattr(f, k, v.ptr if isinstance(v, capi.DeviceBuffer) else v)
+        f.Twc[:] = list(np.asarray(d["Twc"], np.float64).reshape(16))
+        f.fx, f.fy, f.cx, f.cy, f.bf = [float(x) for x in d["cam"]]
+        f.width, f.height = int(d["width"]), int(d["height"])
+    return F
+
+
+class LocalMap:
+    """Owns one rspl_lmap handle: the descriptor bank (one fp64 descriptor per map point id, the one stored at the
+    point's creation), the ordered local map, and the search by projection of a batch of frames against it --
+    alone (``enqueue``) or chained into a Tracker (``track_enqueue``).  Neither enqueue waits for the device.
+    ``device`` < 0: a host-only handle (bank and local-table bookkeeping, no device side)."""
+
+    def __init__(self, max_bank_points=65536, max_local_points=8192, max_keypoints=1024, max_batch=1, device=0,
+                 radius=15.0, max_distance=0.35, max_ratio=0.6):
+        if min(max_bank_points, max_local_points, max_keypoints, max_batch) <= 0:  # before the library is touched
+            raise ValueError(f"LocalMap: capacities {max_bank_points}, {max_local_points}, {max_keypoints}, "
+                             f"{max_batch} must be positive")
+        self.max_local_points, self.max_keypoints, self.max_batch = int(max_local_points), int(max_keypoints), int(max_batch)
+        self._lib = capi.load()
+        self._h = C.c_void_p()
+        cfg = capi.LmapConfig(int(max_bank_points), self.max_local_points, self.max_keypoints, self.max_batch, device,
+                              radius, max_distance, max_ratio)
+        capi.check(self._lib.rspl_lmap_create(C.byref(cfg), C.byref(self._h)), "rspl_lmap_create")
+        self._batch = 0
+        self.n_local = 0
+
+    def store(self, ids, keypoints, d_features, stream=None):
+        """Mappoint::SetDescriptor at creation: the descriptors of records ``keypoints`` of the device records
+        ``d_features`` [cap, 259] become those of map points ``ids``."""
+        a, k = np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(keypoints, np.int32)
+        if a.shape != k.shape:
+            raise ValueError("LocalMap.store: ids and keypoints differ in length")
+        d = d_features.ptr if isinstance(d_features, capi.DeviceBuffer) else d_features
+        capi.check(self._lib.rspl_lmap_store(self._h, len(a), a.ctypes.data, k.ctypes.data, d, _stream_handle(stream)),
+                   "rspl_lmap_store")
+
+    def store_host(self, ids, descriptors):
+        a = np.ascontiguousarray(ids, np.int32)
+        D = np.ascontiguousarray(descriptors, np.float64).reshape(-1, 256)
+        if len(a) != len(D):
+            raise ValueError("LocalMap.store_host: ids and descriptors differ in length")
+        capi.check(self._lib.rspl_lmap_store_host(self._h, len(a), a.ctypes.data, D.ctypes.data), "rspl_lmap_store_host")
+
+    def bank_size(self) -> int:
+        n = C.c_int()
+        capi.check(self._lib.rspl_lmap_bank_size(self._h, C.byref(n)), "rspl_lmap_bank_size")
+        return n.value
+
+    def set_local(self, ids, positions, stream=None):
+        """The local map in order: ids [n] and world positions [n, 3]; every id must have a descriptor."""
+        a = np.ascontiguousarray(ids, np.int32)
+        P = np.ascontiguousarray(positions, np.float64).reshape(-1, 3)
+        if len(a) != len(P):
+            raise ValueError("LocalMap.set_local: ids and positions differ in length")
+        capi.check(self._lib.rspl_lmap_set_local(self._h, len(a), a.ctypes.data, P.ctypes.data, _stream_handle(stream)),
+                   "rspl_lmap_set_local")
+        self.n_local = len(a)
+
+    def enqueue(self, frames, stream=None):
+        """frames: list of dicts with the device addresses ``d_features``, ``d_n1``, ``d_point_id``, ``d_point_xyz``
+        (ints or capi.DeviceBuffer), optional ``d_u_right`` (None: no dxr term) and ``d_point_good``, ``Twc``
+        [4, 4], ``cam`` = (fx, fy, cx, cy, bf), ``width``, ``height``."""
+        capi.check(self._lib.rspl_lmap_enqueue(self._h, len(frames), _lmap_frames(frames), _stream_handle(stream)),
+                   "rspl_lmap_enqueue")
+        self._batch = len(frames)
+
+    def track_enqueue(self, tracker: "Tracker", frames, track_frames, stream=None):
+        """The chain: search, merge into ``tracker``'s keyframe slots, then the tracking step.  ``track_frames``:
+        Tracker.enqueue's dicts (``slot``, ``d_features``, ``d_n1``, optional ``d_u_right``, ``cam``, ``last_Twc``,
+        thresholds); their indices are the handle's own.  Results: ``tracker.fetch()`` and ``fetch()``."""
+        if len(frames) != len(track_frames):
+            raise ValueError("LocalMap.track_enqueue: frames and track_frames differ in length")
+        T = tracker._frame_descs(track_frames)  # (their d_idx0 / d_idx1 are ignored by the library)
+        capi.check(self._lib.rspl_lmap_track_enqueue(self._h, tracker._h, len(frames), _lmap_frames(frames), T,
+                                                     _stream_handle(stream)), "rspl_lmap_track_enqueue")
+        self._batch = len(frames)
+        tracker._enqueued_by(len(frames))
+
+    def fetch(self):
+        """Wait for the last enqueue.  One dict per frame: n_keypoints, n_selected, n_projected, n_with_candidates,
+        n_good, good_kp / good_point (the good projections in local order: keypoint, local index) and assoc_id
+        (the merged table: map point id per keypoint or -1)."""
+        if self._batch == 0:
+            return []
+        R = (capi.LmapResult * self._batch)()
+        arrs = []
+        for r in R:
+            a = (np.full(self.max_local_points, -1, np.int32), np.full(self.max_local_points, -1, np.int32),
+                 np.full(self.max_keypoints, -1, np.int32))
+            r.good_kp, r.good_point, r.assoc_id = (v.ctypes.data for v in a)
+            arrs.append(a)
+        capi.check(self._lib.rspl_lmap_fetch(self._h, R), "rspl_lmap_fetch")
+        return [dict(n_keypoints=r.n_keypoints, n_selected=r.n_selected, n_projected=r.n_projected,
+                     n_with_candidates=r.n_with_candidates, n_good=r.n_good, good_kp=a[0][:r.n_good].copy(),
+                     good_point=a[1][:r.n_good].copy(), assoc_id=a[2][:r.n_keypoints].copy()) for r, a in zip(R, arrs)]
+
+    def debug_points(self, frame=0):
+        """frame ``frame`` of the last fetched enqueue, per local point: dict(status LMAP_*, best_idx, best, second)"""
+        n = max(self.n_local, 1)
+        st, bi, b, s = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n), np.zeros(n)
+        capi.check(self._lib.rspl_lmap_debug_points(self._h, frame, st.ctypes.data, bi.ctypes.data, b.ctypes.data,
+                                                    s.ctypes.data), "rspl_lmap_debug_points")
+        n = self.n_local
+        return dict(status=st[:n], best_idx=bi[:n], best=b[:n], second=s[:n])
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.rspl_lmap_destroy(self._h)
+            self._h = C.c_void_p()
+
+
+def lmap_search_host(features, point_id, local_ids, local_pos, local_desc, Twc, cam, width, height, u_right=None,
+                     radius=15.0, max_distance=0.35, max_ratio=0.6):
+    """rspl_lmap_debug_search_host: the host instantiation of the search text (no device is touched).
+    features [n1, 259]; returns dict(status, best_idx, best, second) per local point."""
+    F = np.ascontiguousarray(features, np.float64).reshape(-1, 259)
+    pid = np.ascontiguousarray(point_id, np.int32)
+    ids = np.ascontiguousarray(local_ids, np.int32)
+    pos = np.ascontiguousarray(local_pos, np.float64).reshape(-1, 3)
+    D = np.ascontiguousarray(local_desc, np.float64).reshape(-1, 256)
+    ur = np.ascontiguousarray(u_right, np.float64) if u_right is not None else None
+    if len(pid) != len(F) or not (len(ids) == len(pos) == len(D)) or (ur is not None and len(ur) != len(F)):
+        raise ValueError("lmap_search_host: array lengths differ")
+    p = capi.LmapHostProblem()
+    p.n_keypoints, p.features, p.point_id = len(F), F.ctypes.data, pid.ctypes.data
+    p.u_right = ur.ctypes.data if ur is not None else None
+    p.n_local, p.local_ids, p.local_pos, p.local_desc = len(ids), ids.ctypes.data, pos.ctypes.data, D.ctypes.data
+    p.Twc[:] = list(np.asarray(Twc, np.float64).reshape(16))
+    p.fx, p.fy, p.cx, p.cy, p.bf = [float(x) for x in cam]
+    p.width, p.height = int(width), int(height)
+    p.radius, p.max_distance, p.max_ratio = radius, max_distance, max_ratio
+    n = max(len(ids), 1)
+    st, bi, b, s = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n), np.zeros(n)
+    capi.check(capi.load().rspl_lmap_debug_search_host(C.byref(p), st.ctypes.data, bi.ctypes.data, b.ctypes.data,
+                                                       s.ctypes.data), "rspl_lmap_debug_search_host")
+    n = len(ids)
+    return dict(status=st[:n], best_idx=bi[:n], best=b[:n], second=s[:n])
+
+
+def TrackLocalMap(map_, local_map: LocalMap, tracker: "Tracker", frame: dict, ref_keyframe: Optional[int] = None,
+                  min_num_match=10, num_inlier_thr=10, stream=None):
+    """Reference-shaped MapBuilder::TrackLocalMap (map_builder.cc:753-785) for one frame.
+
+    ``frame``: dict with the device addresses ``d_features``, ``d_n1``, ``d_point_id``, ``d_point_xyz`` (optional
+    ``d_u_right``, ``d_point_good``, ``d_track_u_right`` -- the pose optimisation's stereo observations), ``Twc`` (the
+    pose to project with, also the last pose of the 0.5 m gate unless ``last_Twc`` is given), ``cam``, ``width``,
+    ``height`` and optional ``slot``.  ``ref_keyframe``: when given, the local map is first rebuilt from ``map_``
+    (UpdateLocalKeyframes / UpdateLocalMappoints; every point needs a descriptor in the bank); None keeps the local
+    map as it was set.  Returns (n_inliers or -1, result): -1 with fewer than 3 good projections or unless
+    n_inliers > min_num_match and n_inliers > num_inlier_thr; on success result holds ``pose_q``, ``pose_p``,
+    ``track_id`` (per keypoint, -1: none) and the search's counts."""
+    if ref_keyframe is not None:
+        ids, pos = map_.LocalMappoints(ref_keyframe)
+        local_map.set_local(ids, pos, stream)
+    tf = dict(slot=frame.get("slot", 0), d_features=frame["d_features"], d_n1=frame["d_n1"],
+              d_u_right=frame.get("d_track_u_right"), cam=frame["cam"], last_Twc=frame.get("last_Twc", frame["Twc"]),
+              min_num_match=min_num_match)
+    local_map.track_enqueue(tracker, [frame], [tf], stream)
+    t, s = tracker.fetch()[0], local_map.fetch()[0]
+    out = dict(s, n_inliers=t["n_inliers"], pose_set=t["pose_set"])
+    if s["n_good"] < 3:
+        return -1, out
+    n = t["n_inliers"]
+    if not (n > min_num_match and n > num_inlier_thr):
+        return -1, out
+    out.update(pose_q=t["pose_q"], pose_p=t["pose_p"], track_id=t["track_id"])
+    return n, out
 
 
 from .synthetic import stereo_window  # noqa: E402  (Camera's disparity window from bf and the depth thresholds)

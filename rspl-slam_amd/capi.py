@@ -66,6 +66,9 @@ EXPORTS = [
     "rspl_rcf_debug_logits", "rspl_rcf_debug_tile_rows", "rspl_rcf_profile", "rspl_rcf_stage_times",
     "rspl_fm_create", "rspl_fm_destroy", "rspl_fm_solve", "rspl_fm_enqueue", "rspl_fm_fetch",
     "rspl_fm_debug_subsets", "rspl_fm_debug_seven_point", "rspl_fm_debug_hypotheses",
+    "rspl_lmap_create", "rspl_lmap_destroy", "rspl_lmap_store", "rspl_lmap_store_host", "rspl_lmap_bank_size",
+    "rspl_lmap_set_local", "rspl_lmap_enqueue", "rspl_lmap_fetch", "rspl_lmap_debug_points", "rspl_lmap_track_enqueue",
+    "rspl_lmap_debug_search_host", "rspl_map_reference_keyframe", "rspl_map_local_mappoints",
 ]
 
 
@@ -227,6 +230,33 @@ class RectConfig(C.Structure):
 class RcfConfig(C.Structure):
     _fields_ = [("max_height", C.c_int), ("max_width", C.c_int), ("max_batch", C.c_int), ("precision", C.c_int),
                 ("output", C.c_int), ("device", C.c_int)]
+
+
+class LmapConfig(C.Structure):
+    _fields_ = [("max_bank_points", C.c_int), ("max_local_points", C.c_int), ("max_keypoints", C.c_int),
+                ("max_batch", C.c_int), ("device", C.c_int), ("radius", C.c_double), ("max_distance", C.c_double),
+                ("max_ratio", C.c_double)]
+
+
+class LmapFrame(C.Structure):
+    _fields_ = [("d_features", C.c_void_p), ("d_n1", C.c_void_p), ("d_u_right", C.c_void_p),
+                ("d_point_id", C.c_void_p), ("d_point_xyz", C.c_void_p), ("d_point_good", C.c_void_p),
+                ("Twc", C.c_double * 16), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("bf", C.c_double), ("width", C.c_int), ("height", C.c_int)]
+
+
+class LmapResult(C.Structure):
+    _fields_ = [("n_keypoints", C.c_int), ("n_selected", C.c_int), ("n_projected", C.c_int),
+                ("n_with_candidates", C.c_int), ("n_good", C.c_int), ("good_kp", C.c_void_p),
+                ("good_point", C.c_void_p), ("assoc_id", C.c_void_p)]
+
+
+class LmapHostProblem(C.Structure):
+    _fields_ = [("n_keypoints", C.c_int), ("features", C.c_void_p), ("u_right", C.c_void_p), ("point_id", C.c_void_p),
+                ("n_local", C.c_int), ("local_ids", C.c_void_p), ("local_pos", C.c_void_p), ("local_desc", C.c_void_p),
+                ("Twc", C.c_double * 16), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("bf", C.c_double), ("width", C.c_int), ("height", C.c_int),
+                ("radius", C.c_double), ("max_distance", C.c_double), ("max_ratio", C.c_double)]
 
 
 class RsplError(RuntimeError):
@@ -402,6 +432,21 @@ def load(path: pathlib.Path = LIB_PATH):
         lib.rspl_rcf_debug_tile_rows.argtypes = [vp, ip]
         lib.rspl_rcf_profile.argtypes = [vp, ip]
         lib.rspl_rcf_stage_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(ip)]
+    if hasattr(lib, "rspl_lmap_create"):
+        lib.rspl_lmap_create.argtypes = [C.POINTER(LmapConfig), C.POINTER(vp)]
+        lib.rspl_lmap_destroy.argtypes = [vp]
+        lib.rspl_lmap_destroy.restype = None
+        lib.rspl_lmap_store.argtypes = [vp, ip, vp, vp, vp, vp]
+        lib.rspl_lmap_store_host.argtypes = [vp, ip, vp, vp]
+        lib.rspl_lmap_bank_size.argtypes = [vp, C.POINTER(ip)]
+        lib.rspl_lmap_set_local.argtypes = [vp, ip, vp, vp, vp]
+        lib.rspl_lmap_enqueue.argtypes = [vp, ip, vp, vp]
+        lib.rspl_lmap_fetch.argtypes = [vp, vp]
+        lib.rspl_lmap_debug_points.argtypes = [vp, ip, vp, vp, vp, vp]
+        lib.rspl_lmap_track_enqueue.argtypes = [vp, vp, ip, vp, vp, vp]
+        lib.rspl_lmap_debug_search_host.argtypes = [C.POINTER(LmapHostProblem), vp, vp, vp, vp]
+        lib.rspl_map_reference_keyframe.argtypes = [vp, ip, ip, vp, ip, C.POINTER(ip), C.POINTER(ip)]
+        lib.rspl_map_local_mappoints.argtypes = [vp, ip, vp, vp, ip, C.POINTER(ip)]
     _lib = lib
     return lib
 

@@ -1485,3 +1485,59 @@ extern "C" int rspl_map_save_trajectory(const rspl_map* m, const char* path) {
   fclose(f);
   return RSPL_OK;
 }
+
+// MapBuilder::UpdateReferenceFrame (map_builder.cc:684-712).  The reference counts in a std::map keyed by
+// FramePtr and keeps the first strictly larger count of its pointer-ordered walk; here, as for the covisibility
+// ties above, the walk is in ascending frame id.
+extern "C" int rspl_map_reference_keyframe(const rspl_map* m, int current_frame_id, int n, const int32_t* point_ids,
+                                           int current_ref, int* ref, int* changed) {
+  RSPL_CHECK_ARG(m && ref && changed && (n == 0 || point_ids) && n >= 0, "rspl_map_reference_keyframe: bad argument");
+  std::map<int, int> votes;
+  for (int i = 0; i < n; i++) {
+    auto it = point_ids[i] < 0 ? m->mp.end() : m->mp.find(point_ids[i]);
+    if (it == m->mp.end() || it->second.type == kBad) continue;  // !mpt || mpt->IsBad()
+    for (auto& kv : it->second.obs) {
+      if (kv.first == current_frame_id || !m->kf.count(kv.first)) continue;
+      votes[kv.first]++;
+    }
+  }
+  int best = current_ref, best_n = -1;
+  for (auto& kv : votes)
+    if (kv.second > best_n) {
+      best = kv.first;
+      best_n = kv.second;
+    }
+  *ref = best;
+  *changed = best != current_ref;
+  return RSPL_OK;
+}
+
+// MapBuilder::UpdateLocalKeyframes + UpdateLocalMappoints (map_builder.cc:714-734): tracking_frame_id's
+// "seen in this walk" mark is a set here
+extern "C" int rspl_map_local_mappoints(const rspl_map* m, int ref_frame_id, int32_t* ids, double* positions, int cap,
+                                        int* n) {
+  RSPL_CHECK_ARG(m && n && cap >= 0, "rspl_map_local_mappoints: bad argument");
+  auto fit = m->kf.find(ref_frame_id);
+  RSPL_CHECK_ARG(fit != m->kf.end(), "rspl_map_local_mappoints: unknown frame %d", ref_frame_id);
+  std::vector<const MPoint*> out;
+  std::set<int> seen;
+  for (auto& wc : fit->second.oconn) {  // GetOrderedConnections(-1): ascending (weight, frame id)
+    auto kit = m->kf.find(wc.second);
+    if (kit == m->kf.end()) continue;
+    for (int id : kit->second.mpt) {
+      auto pit = id < 0 ? m->mp.end() : m->mp.find(id);
+      if (pit == m->mp.end() || pit->second.type != kGood) continue;  // mpt && mpt->IsValid()
+      if (seen.insert(id).second) out.push_back(&pit->second);
+    }
+  }
+  *n = (int)out.size();
+  if (cap < *n) {
+    set_error("rspl_map_local_mappoints: capacity %d < %d local map points", cap, *n);
+    return RSPL_E_CAPACITY;
+  }
+  for (size_t i = 0; i < out.size(); i++) {
+    if (ids) ids[i] = out[i]->id;
+    if (positions) memcpy(positions + 3 * i, out[i]->p, sizeof(double) * 3);
+  }
+  return RSPL_OK;
+}

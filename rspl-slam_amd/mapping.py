@@ -239,6 +239,29 @@ class Map:
     def UpdateFrameConnection(self, frame_id: int):
         capi.check(self._lib.rspl_map_update_connections(self._h, frame_id), "rspl_map_update_connections")
 
+    # ---- local map selection (MapBuilder::UpdateReferenceFrame / UpdateLocalKeyframes / UpdateLocalMappoints) ----
+    def ReferenceKeyframe(self, current_frame_id: int, point_ids, current_ref: int):
+        """The observer of the frame's non-bad map points (``point_ids``: id per keypoint or -1) with the most
+        votes, the current frame and unknown frames aside; ties: the lowest frame id.  Returns (ref, changed)."""
+        a = np.ascontiguousarray(point_ids, np.int32)
+        ref, changed = C.c_int(), C.c_int()
+        capi.check(self._lib.rspl_map_reference_keyframe(self._h, current_frame_id, len(a), a.ctypes.data, current_ref,
+                                                         C.byref(ref), C.byref(changed)), "rspl_map_reference_keyframe")
+        return ref.value, bool(changed.value)
+
+    def LocalMappoints(self, ref_frame_id: int, cap: Optional[int] = None):
+        """The Good map points of the reference keyframe's neighbours in GetOrderedConnections(-1) order, slots in
+        keypoint order, first occurrence only: (ids int32 [n], positions [n, 3]).  ``cap``: the caller's capacity
+        (an RsplError when the local map is larger); None: as many as there are."""
+        n = C.c_int()
+        if cap is None:
+            self._lib.rspl_map_local_mappoints(self._h, ref_frame_id, None, None, 0, C.byref(n))  # the count
+            cap = n.value
+        ids, pos = np.zeros(cap, np.int32), np.zeros((cap, 3))
+        capi.check(self._lib.rspl_map_local_mappoints(self._h, ref_frame_id, ids.ctypes.data, pos.ctypes.data, cap,
+                                                      C.byref(n)), "rspl_map_local_mappoints")
+        return ids[:n.value].copy(), pos[:n.value].copy()
+
     # ---- Map::LocalMapOptimization ----
     def LocalMapOptimization(self, frame_id: int, ba) -> dict:
         """The whole of Map::LocalMapOptimization(new_frame) with the GPU local BA of `ba` (LocalBA)."""
