@@ -1530,6 +1530,75 @@ int rspl_map_reference_keyframe(const rspl_map* m, int current_frame_id, int n, 
 int rspl_map_local_mappoints(const rspl_map* m, int ref_frame_id, int32_t* ids, double* positions, int cap, int* n);
 
 
+/* ------------------------------------------------------------------------ */
+/* Relocalisation: the search of the local table by descriptor alone.  The   */
+/* reference has no such stage; parity is with           */
+/* tests/reloc_ref.py.  D[i][p] = 2 (1 - q_i . d_p) for keypoint i of the    */
+/* frame and entry p of the table rspl_lmap_set_local set:                   */
+/*   per keypoint  best, arg (a tie keeps the lowest p), second (the second  */
+/*                 smallest value; 4.0 where nothing is below it)            */
+/*   per point     kbest, the lowest i that attains min_i D[i][p]            */
+/*   pass          best < max_distance and best < max_ratio * second         */
+/*   match         pass and (mutual == 0 or kbest[arg] == i)                 */
+/* The device evaluates D on fp64 MFMA; its distances agree with the host's  */
+/* fixed summation order to rounding (1e-13), its decisions exactly wherever */
+/* no two candidates are closer than that.                                   */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  double max_distance; /* 0.35 */
+  double max_ratio;    /* 0.6 */
+  int mutual;          /* != 0: a match must also be its point's nearest keypoint */
+} rspl_lmap_global_params;
+
+typedef struct {
+  int n_keypoints; /* as the device read it (clamped to max_keypoints) */
+  int n_local;
+  int n_pass;
+  int n_matched;
+  /* caller arrays (each may be NULL) */
+  int32_t* arg;         /* [max_keypoints] local index of the nearest point or -1; the first n_keypoints ... */
+  double* best;         /* ... of these four are written */
+  double* second;
+  int32_t* match;       /* local index of the match or -1 */
+  int32_t* kbest;       /* [max_local_points] nearest keypoint per local point or -1; the first n_local */
+  /* the matches in ascending keypoint order, the first n_matched of each [max_keypoints] array */
+  int32_t* match_kp;    /* keypoint index */
+  int32_t* match_local; /* local index */
+  int32_t* match_id;    /* map point id */
+  double* match_pos;    /* [..][3] its position */
+  double* match_xy;     /* [..][2] the keypoint (rows 1, 2 of its record) */
+} rspl_lmap_global_result;
+
+/* frames[b].d_features and d_n1 are read; every other field of rspl_lmap_frame is ignored.  Same stream rules as
+ * rspl_lmap_enqueue: no host synchronisation, a device-side wait for the handle's last store / set_local, and one
+ * enqueue in flight per handle whatever its kind (RSPL_E_ARG otherwise; rspl_lmap_set_local is refused in
+ * between).  The first call allocates the search's partial arrays.  A host-only handle is refused. */
+int rspl_lmap_global_enqueue(rspl_lmap* h, int batch, const rspl_lmap_frame* frames,
+                             const rspl_lmap_global_params* params, void* stream);
+/* Wait for the last global enqueue; results[b] receives frame b. */
+int rspl_lmap_global_fetch(rspl_lmap* h, rspl_lmap_global_result* results);
+
+/* debug (parity tests): the same contract on host arrays, distances in the fixed summation order of
+ * csrc/lmap_match.hpp -- equal to tests/reloc_ref.py bit for bit; no device is touched */
+typedef struct {
+  int n_keypoints;
+  const double* features;   /* [n_keypoints][259] */
+  int n_local;
+  const int32_t* local_ids; /* [n_local] */
+  const double* local_pos;  /* [n_local][3] */
+  const double* local_desc; /* [n_local][256] */
+} rspl_lmap_global_host_problem;
+int rspl_lmap_debug_global_host(const rspl_lmap_global_host_problem* p, const rspl_lmap_global_params* params,
+                                rspl_lmap_global_result* result);
+/* the tile geometry of the device search for a handle of these capacities: bank rows per workgroup, keypoints per
+ * workgroup, descriptor entries per LDS slab (each may be NULL) */
+int rspl_lmap_debug_global_plan(int max_keypoints, int max_local_points, int* chunk_rows, int* qtile_rows,
+                                int* k_slab);
+
+/* Every Good map point in ascending id order (the candidate table of a relocalisation over the whole map); the
+ * cap / *n protocol of rspl_map_local_mappoints. */
+int rspl_map_good_mappoints(const rspl_map* m, int32_t* ids, double* positions, int cap, int* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1133,6 +1133,32 @@ class LocalMap:
                      n_with_candidates=r.n_with_candidates, n_good=r.n_good, good_kp=a[0][:r.n_good].copy(),
                      good_point=a[1][:r.n_good].copy(), assoc_id=a[2][:r.n_keypoints].copy()) for r, a in zip(R, arrs)]
 
+    def global_enqueue(self, frames, max_distance=0.35, max_ratio=0.6, mutual=True, stream=None):
+        """The search of the local table by descriptor alone (relocalisation): mutual nearest neighbours with a
+        ratio test.  frames: ``enqueue``'s dicts, of which only ``d_features`` and ``d_n1`` are read.  Never waits
+        for the device; ``global_fetch`` is next."""
+        F = (capi.LmapFrame * max(len(frames), 1))()
+        for f, d in zip(F, frames):
+            for k in ("d_features", "d_n1"):
+                v = d.get(k)
+                setattr(f, k, v.ptr if isinstance(v, capi.DeviceBuffer) else v)
+        gp = capi.LmapGlobalParams(float(max_distance), float(max_ratio), int(bool(mutual)))
+        capi.check(self._lib.rspl_lmap_global_enqueue(self._h, len(frames), F, C.byref(gp), _stream_handle(stream)),
+                   "rspl_lmap_global_enqueue")
+        self._gbatch = len(frames)
+
+    def global_fetch(self):
+        """Wait for the last global enqueue.  One dict per frame: the counts n_keypoints, n_local, n_pass, n_matched;
+        per keypoint arg, best, second, match (local index or -1); per local point kbest; and the matches in
+        ascending keypoint order: match_kp, match_local, match_id, match_pos [n, 3], match_xy [n, 2]."""
+        B = getattr(self, "_gbatch", 0)
+        if B == 0:
+            return []
+        R = (capi.LmapGlobalResult * B)()
+        arrs = [_global_result_arrays(r, self.max_keypoints, self.max_local_points) for r in R]
+        capi.check(self._lib.rspl_lmap_global_fetch(self._h, R), "rspl_lmap_global_fetch")
+        return [_global_result_dict(r, a) for r, a in zip(R, arrs)]
+
     def debug_points(self, frame=0):
         """frame ``frame`` of the last fetched enqueue, per local point: dict(status LMAP_*, best_idx, best, second)"""
         n = max(self.n_local, 1)
@@ -1174,6 +1200,87 @@ def lmap_search_host(features, point_id, local_ids, local_pos, local_desc, Twc, 
                                                        s.ctypes.data), "rspl_lmap_debug_search_host")
     n = len(ids)
     return dict(status=st[:n], best_idx=bi[:n], best=b[:n], second=s[:n])
+
+
+def _global_result_arrays(r, K, L):
+    K, L = max(K, 1), max(L, 1)
+    a = dict(arg=np.full(K, -1, np.int32), best=np.full(K, 4.0), second=np.full(K, 4.0), match=np.full(K, -1, np.int32),
+             kbest=np.full(L, -1, np.int32), match_kp=np.full(K, -1, np.int32), match_local=np.full(K, -1, np.int32),
+             match_id=np.full(K, -1, np.int32), match_pos=np.zeros((K, 3)), match_xy=np.zeros((K, 2)))
+    for k, v in a.items():
+        setattr(r, k, v.ctypes.data)
+    return a
+
+
+def _global_result_dict(r, a):
+    out = dict(n_keypoints=r.n_keypoints, n_local=r.n_local, n_pass=r.n_pass, n_matched=r.n_matched)
+    for k in ("arg", "best", "second", "match"):
+        out[k] = a[k][:r.n_keypoints].copy()
+    out["kbest"] = a["kbest"][:r.n_local].copy()
+    for k in ("match_kp", "match_local", "match_id", "match_pos", "match_xy"):
+        out[k] = a[k][:r.n_matched].copy()
+    return out
+
+
+def lmap_global_host(features, local_ids, local_pos, local_desc, max_distance=0.35, max_ratio=0.6, mutual=True):
+    """rspl_lmap_debug_global_host: the global search's contract on host arrays, distances in the fixed summation
+    order (no device is touched).  features [n1, 259]; returns ``LocalMap.global_fetch``'s dict."""
+    F = np.ascontiguousarray(features, np.float64).reshape(-1, 259)
+    ids = np.ascontiguousarray(local_ids, np.int32)
+    pos = np.ascontiguousarray(local_pos, np.float64).reshape(-1, 3)
+    D = np.ascontiguousarray(local_desc, np.float64).reshape(-1, 256)
+    if not (len(ids) == len(pos) == len(D)):
+        raise ValueError("lmap_global_host: array lengths differ")
+    p = capi.LmapGlobalHostProblem(len(F), F.ctypes.data, len(ids), ids.ctypes.data, pos.ctypes.data, D.ctypes.data)
+    gp = capi.LmapGlobalParams(float(max_distance), float(max_ratio), int(bool(mutual)))
+    r = capi.LmapGlobalResult()
+    a = _global_result_arrays(r, len(F), len(ids))
+    capi.check(capi.load().rspl_lmap_debug_global_host(C.byref(p), C.byref(gp), C.byref(r)),
+               "rspl_lmap_debug_global_host")
+    return _global_result_dict(r, a)
+
+
+def lmap_global_plan(max_keypoints, max_local_points):
+    """rspl_lmap_debug_global_plan: (chunk_rows, qtile_rows, k_slab) of the device search for these capacities"""
+    c, q, k = C.c_int(), C.c_int(), C.c_int()
+    capi.check(capi.load().rspl_lmap_debug_global_plan(int(max_keypoints), int(max_local_points), C.byref(c),
+                                                       C.byref(q), C.byref(k)), "rspl_lmap_debug_global_plan")
+    return c.value, q.value, k.value
+
+
+def Relocalise(map_, local_map: LocalMap, tracker: "Tracker", pnp: "PnP", frame: dict, candidates=None,
+               ref_keyframe: Optional[int] = None, min_num_match=10, num_inlier_thr=10, stream=None):
+    """Find the camera again without a pose prior (the reference has no such stage: its tracking gives up for good).
+
+    1. candidates: ``(ids, positions)`` sets the local table, ``"map"`` takes ``map_.GoodMappoints()``, None keeps
+       the table as set; 2. the global descriptor search (``LocalMap.global_enqueue``) -- fewer than
+       max(8, min_num_match) matches: (-1, info), stage "search"; 3. ``pnp.solve`` on the matches (100 iterations,
+       20 px, 0.99) -- fewer than min_num_match inliers: (-1, info), stage "pnp"; 4. ``TrackLocalMap`` with
+       Twc = last_Twc = PnP's pose (``ref_keyframe`` as there), whose (n_inliers, result) is returned, stage "track".
+    ``frame``: TrackLocalMap's dict (its ``Twc`` / ``last_Twc`` are replaced); ``info`` / result carry ``stage``,
+    ``n_matched`` and, from step 3 on, ``pnp_inliers`` and ``pnp_Twc``.  Two host synchronisations by design."""
+    if isinstance(candidates, str):
+        if candidates != "map":
+            raise ValueError(f"Relocalise: candidates {candidates!r}")
+        candidates = map_.GoodMappoints()
+    if candidates is not None:
+        local_map.set_local(candidates[0], candidates[1], stream)
+    local_map.global_enqueue([frame], stream=stream)
+    g = local_map.global_fetch()[0]
+    info = dict(stage="search", n_matched=g["n_matched"], n_pass=g["n_pass"])
+    if g["n_matched"] < max(8, min_num_match):
+        return -1, info
+    cam = frame["cam"]
+    k, Rwc, twc, inl, _ = pnp.solve([(tuple(cam[:4]), g["match_pos"], g["match_xy"])], 100, 20.0, 0.99)[0]
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = Rwc, twc
+    info.update(stage="pnp", pnp_inliers=k, pnp_Twc=T)
+    if k < min_num_match:
+        return -1, info
+    n, out = TrackLocalMap(map_, local_map, tracker, dict(frame, Twc=T, last_Twc=T), ref_keyframe, min_num_match,
+                           num_inlier_thr, stream)
+    out.update(info, stage="track")
+    return n, out
 
 
 def TrackLocalMap(map_, local_map: LocalMap, tracker: "Tracker", frame: dict, ref_keyframe: Optional[int] = None,

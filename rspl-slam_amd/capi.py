@@ -69,6 +69,8 @@ EXPORTS = [
     "rspl_lmap_create", "rspl_lmap_destroy", "rspl_lmap_store", "rspl_lmap_store_host", "rspl_lmap_bank_size",
     "rspl_lmap_set_local", "rspl_lmap_enqueue", "rspl_lmap_fetch", "rspl_lmap_debug_points", "rspl_lmap_track_enqueue",
     "rspl_lmap_debug_search_host", "rspl_map_reference_keyframe", "rspl_map_local_mappoints",
+    "rspl_lmap_global_enqueue", "rspl_lmap_global_fetch", "rspl_lmap_debug_global_host", "rspl_lmap_debug_global_plan",
+    "rspl_map_good_mappoints",
 ]
 
 
@@ -259,6 +261,22 @@ class LmapHostProblem(C.Structure):
                 ("radius", C.c_double), ("max_distance", C.c_double), ("max_ratio", C.c_double)]
 
 
+class LmapGlobalParams(C.Structure):
+    _fields_ = [("max_distance", C.c_double), ("max_ratio", C.c_double), ("mutual", C.c_int)]
+
+
+class LmapGlobalResult(C.Structure):
+    _fields_ = [("n_keypoints", C.c_int), ("n_local", C.c_int), ("n_pass", C.c_int), ("n_matched", C.c_int),
+                ("arg", C.c_void_p), ("best", C.c_void_p), ("second", C.c_void_p), ("match", C.c_void_p),
+                ("kbest", C.c_void_p), ("match_kp", C.c_void_p), ("match_local", C.c_void_p),
+                ("match_id", C.c_void_p), ("match_pos", C.c_void_p), ("match_xy", C.c_void_p)]
+
+
+class LmapGlobalHostProblem(C.Structure):
+    _fields_ = [("n_keypoints", C.c_int), ("features", C.c_void_p), ("n_local", C.c_int), ("local_ids", C.c_void_p),
+                ("local_pos", C.c_void_p), ("local_desc", C.c_void_p)]
+
+
 class RsplError(RuntimeError):
     pass
 
@@ -447,6 +465,13 @@ def load(path: pathlib.Path = LIB_PATH):
         lib.rspl_lmap_debug_search_host.argtypes = [C.POINTER(LmapHostProblem), vp, vp, vp, vp]
         lib.rspl_map_reference_keyframe.argtypes = [vp, ip, ip, vp, ip, C.POINTER(ip), C.POINTER(ip)]
         lib.rspl_map_local_mappoints.argtypes = [vp, ip, vp, vp, ip, C.POINTER(ip)]
+    if hasattr(lib, "rspl_lmap_global_enqueue"):
+        lib.rspl_lmap_global_enqueue.argtypes = [vp, ip, vp, C.POINTER(LmapGlobalParams), vp]
+        lib.rspl_lmap_global_fetch.argtypes = [vp, vp]
+        lib.rspl_lmap_debug_global_host.argtypes = [C.POINTER(LmapGlobalHostProblem), C.POINTER(LmapGlobalParams),
+                                                    C.POINTER(LmapGlobalResult)]
+        lib.rspl_lmap_debug_global_plan.argtypes = [ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
+        lib.rspl_map_good_mappoints.argtypes = [vp, vp, vp, ip, C.POINTER(ip)]
     _lib = lib
     return lib
 

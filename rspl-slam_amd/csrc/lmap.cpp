@@ -4,6 +4,7 @@
 // id, the ordered local map resolved to bank rows on the host, and search | merge | the tracking chain of
 // rspl_track_enqueue as one stream-ordered sequence with no host work in between.
 // rspl_lmap_debug_search_host is the host instantiation of the search text (lmap_match.hpp).
+// rspl_lmap_global_* (lmap_reloc.cpp) is the second reader of the bank; the handle is lmap_handle.hpp's.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -11,38 +12,9 @@
 #include <vector>
 
 #include "common.hpp"
-#include "lmap_kernels.hpp"
+#include "lmap_handle.hpp"
 
 using namespace rspl;
-
-struct rspl_lmap {
-  rspl_lmap_config cfg{};
-  bool host_only = false;
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr, store_ev = nullptr, local_ev = nullptr;
-  Arena arena;
-  PinnedArena pinned;
-  lmap::Args a{};
-  // the bank: id -> row; rows are handed out in order and never freed
-  std::unordered_map<int, int> row_of;
-  double* bank = nullptr;             // device [max_bank_points][256]
-  std::vector<double> host_bank;      // a host-only handle's descriptors
-  // the local map: the device arrays (pieces of `arena`) and their host-mapped staging
-  int n_local = 0;
-  std::vector<int32_t> local_ids;
-  int32_t *d_local_row = nullptr, *d_local_id = nullptr;
-  double* d_local_pos = nullptr;
-  int32_t *s_local_row = nullptr, *s_local_row_dev = nullptr, *s_local_id = nullptr, *s_local_id_dev = nullptr;
-  double *s_local_pos = nullptr, *s_local_pos_dev = nullptr;
-  int32_t *s_pairs = nullptr, *s_pairs_dev = nullptr;  // rspl_lmap_store's (row, keypoint) pairs
-  // host-mapped: the per-frame parameters in, the results out
-  lmap::Param* params = nullptr;
-  lmap::Out* out = nullptr;
-  int32_t *o_good_kp = nullptr, *o_good_point = nullptr, *o_assoc = nullptr;
-  bool pending = false;
-  int batch = 0;        // frames of the last enqueue
-  int batch_local = 0;  // the local map's length at that enqueue
-};
 
 namespace {
 
@@ -109,13 +81,6 @@ int check_enqueue(rspl_lmap* h, int batch, const rspl_lmap_frame* frames, const 
     RSPL_CHECK_ARG(good_frame(fr), "frame %d: bad camera, pose or image size", b);
   }
   return RSPL_OK;
-}
-
-// the last bank store and local-map upload may have gone to other streams than this enqueue's: it waits for both
-// (an event never recorded is complete)
-hipError_t wait_uploads(rspl_lmap* h, hipStream_t st) {
-  const hipError_t e = hipStreamWaitEvent(st, h->store_ev, 0);
-  return e != hipSuccess ? e : hipStreamWaitEvent(st, h->local_ev, 0);
 }
 
 }  // namespace
@@ -217,6 +182,8 @@ extern "C" void rspl_lmap_destroy(rspl_lmap* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   h->arena.release();
   h->pinned.release();
+  h->g_arena.release();
+  h->g_pinned.release();
   for (hipEvent_t e : {h->done, h->store_ev, h->local_ev})
     if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -316,7 +283,7 @@ extern "C" int rspl_lmap_enqueue(rspl_lmap* h, int batch, const rspl_lmap_frame*
   if (batch == 0) return RSPL_OK;
   fill_params(h, batch, frames, nullptr, nullptr, nullptr);
   hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-  RSPL_HIP(wait_uploads(h, st));
+  RSPL_HIP(lmap::wait_uploads(h, st));
   RSPL_HIP(lmap::search(h->a, batch, h->n_local, st));
   RSPL_HIP(hipEventRecord(h->done, st));
   h->pending = true;
@@ -350,7 +317,7 @@ extern "C" int rspl_lmap_track_enqueue(rspl_lmap* h, rspl_track* t, int batch, c
   if (batch == 0) return rspl_track_enqueue(t, 0, tf, stream);
   fill_params(h, batch, frames, kp.data(), ks.data(), kt.data());
   hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-  RSPL_HIP(wait_uploads(h, st));
+  RSPL_HIP(lmap::wait_uploads(h, st));
   RSPL_HIP(lmap::search(h->a, batch, h->n_local, st));
   RSPL_HIP(hipEventRecord(h->done, st));
   h->pending = true;
@@ -359,6 +326,7 @@ extern "C" int rspl_lmap_track_enqueue(rspl_lmap* h, rspl_track* t, int batch, c
 
 extern "C" int rspl_lmap_fetch(rspl_lmap* h, rspl_lmap_result* res) {
   RSPL_CHECK_ARG(h && (res || h->batch == 0), "rspl_lmap_fetch: NULL argument");
+  RSPL_CHECK_ARG(!(h->pending && h->pending_global), "rspl_lmap_fetch: the enqueue in flight is a global one");
   if (h->pending) {
     RSPL_HIP(hipEventSynchronize(h->done));
     h->pending = false;

@@ -1541,3 +1541,22 @@ extern "C" int rspl_map_local_mappoints(const rspl_map* m, int ref_frame_id, int
   }
   return RSPL_OK;
 }
+
+// every Good map point, ascending id (a read-only walk)
+extern "C" int rspl_map_good_mappoints(const rspl_map* m, int32_t* ids, double* positions, int cap, int* n) {
+  RSPL_CHECK_ARG(m && n && cap >= 0, "rspl_map_good_mappoints: bad argument");
+  std::vector<const MPoint*> out;
+  for (auto& kv : m->mp)
+    if (kv.second.type == kGood) out.push_back(&kv.second);
+  std::sort(out.begin(), out.end(), [](const MPoint* a, const MPoint* b) { return a->id < b->id; });
+  *n = (int)out.size();
+  if (cap < *n) {
+    set_error("rspl_map_good_mappoints: capacity %d < %d good map points", cap, *n);
+    return RSPL_E_CAPACITY;
+  }
+  for (size_t i = 0; i < out.size(); i++) {
+    if (ids) ids[i] = out[i]->id;
+    if (positions) memcpy(positions + 3 * i, out[i]->p, sizeof(double) * 3);
+  }
+  return RSPL_OK;
+}

@@ -262,6 +262,18 @@ class Map:
                                                       C.byref(n)), "rspl_map_local_mappoints")
         return ids[:n.value].copy(), pos[:n.value].copy()
 
+    def GoodMappoints(self, cap: Optional[int] = None):
+        """Every Good map point in ascending id order -- the candidate table of a relocalisation over the whole
+        map: (ids int32 [n], positions [n, 3]).  ``cap`` as in ``LocalMappoints``."""
+        n = C.c_int()
+        if cap is None:
+            self._lib.rspl_map_good_mappoints(self._h, None, None, 0, C.byref(n))  # the count
+            cap = n.value
+        ids, pos = np.zeros(cap, np.int32), np.zeros((cap, 3))
+        capi.check(self._lib.rspl_map_good_mappoints(self._h, ids.ctypes.data, pos.ctypes.data, cap, C.byref(n)),
+                   "rspl_map_good_mappoints")
+        return ids[:n.value].copy(), pos[:n.value].copy()
+
     # ---- Map::LocalMapOptimization ----
     def LocalMapOptimization(self, frame_id: int, ba) -> dict:
         """The whole of Map::LocalMapOptimization(new_frame) with the GPU local BA of `ba` (LocalBA)."""
