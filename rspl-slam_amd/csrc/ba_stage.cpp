@@ -291,5 +291,33 @@ size_t pair_offsets(const Active& G, const int* lm_off, const int* lm_pose, cons
   return (size_t)n[nc];
 }
 
+int pack_line_blocks(const int* lm_off, int nq, int nL, int4* ltab) {
+  constexpr int kB = kLineBlk;
+  int n_lblk = 0;
+  int p0 = 0, cnt = 0, gb = -1, ge = 0;
+  auto flush = [&]() {
+    if (gb >= 0 && cnt > 0) ltab[n_lblk++] = make_int4(p0, cnt, gb, ge);
+    gb = -1;
+    cnt = 0;
+  };
+  for (int g = nq; g < nL; g++) {
+    const int k = lm_off[g + 1] - lm_off[g];
+    if (k > kB) {
+      flush();
+      for (int o = 0; o < k; o += kB) ltab[n_lblk++] = make_int4(lm_off[g] + o, std::min(kB, k - o) | (1 << 8), g, g + 1);
+      continue;
+    }
+    if (gb >= 0 && (cnt + k > kB || g - gb >= kB)) flush();
+    if (gb < 0) {
+      p0 = lm_off[g];
+      gb = g;
+    }
+    cnt += k;
+    ge = g + 1;
+  }
+  flush();
+  return n_lblk;
+}
+
 }  // namespace ba
 }  // namespace rspl

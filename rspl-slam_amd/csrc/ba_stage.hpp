@@ -38,6 +38,16 @@ struct Stager {
     int* ginv = nullptr;
   };
   void place(const rspl_ba_problem* pr, const Out& o);
+  // after count(): the reduced numbering of the poses -- pidx[p] (pidx may be null) = the pose's index among the
+  // optimised ones (it has a local edge and is not fixed), else -1; returns their number K
+  int number_poses(const rspl_ba_problem* pr, int* pidx) const {
+    int K = 0;
+    for (int p = 0; p < pr->n_poses; p++) {
+      const int k = (pose_has_edge[p] && !pr->pose_fixed[p]) ? K++ : -1;
+      if (pidx) pidx[p] = k;
+    }
+    return K;
+  }
 
   int E = 0, Ep = 0;
   std::vector<uint8_t> pose_has_edge;  // [np]
@@ -60,6 +70,15 @@ struct Stager {
 // pair_scan counts on the device.  G: nchk / lmchunk / dsub / lmsub / K / npairs / nL set (chunk_geo's fields).
 // pp_off [chunk_count(G) + 1]: the exclusive scan; returns the total.
 size_t pair_offsets(const Active& G, const int* lm_off, const int* lm_pose, const uint8_t* lm_act, int* pp_off);
+
+// Line workgroups (Active::ltab) of the line landmarks [nq, nL) of the staged CSR: consecutive line landmarks
+// packed whole into <= kLineBlk edges (and <= kLineBlk landmarks), so a workgroup sums their blocks itself; a
+// landmark with more edges gets workgroups of its own, flagged split (1 << 8: per-edge records + last-edge
+// ticket).  Entry {first CSR position, edges | split << 8, first landmark, end landmark}; returns their number.
+int pack_line_blocks(const int* lm_off, int nq, int nL, int4* ltab);
+// entries ltab must hold for nl line landmarks with line_edges edges: at most one per line landmark plus one per
+// kLineBlk line edges (a landmark with more edges is split)
+inline size_t line_blocks_bound(size_t nl, size_t line_edges) { return nl + line_edges / kLineBlk + 2; }
 
 }  // namespace ba
 }  // namespace rspl

@@ -37,5 +37,33 @@ inline Se3h inverse(const Se3h& T) {  // SE3Quat::inverse
   return r;
 }
 
+// The caller's pose (q: x y z w, p; T_wc) to the solver's estimate T[8] (T_cw: q w x y z, t, pad) --
+// VertexSE3Expmap estimate = SE3Quat(q, p).inverse() (g2o_optimization.cc:42) -- and back: T_wc =
+// estimate().inverse() (:235-240)
+inline void pose_to_estimate(const double* q_xyzw, const double* p, double* T) {
+  Se3h Twc;
+  Twc.q[0] = q_xyzw[3];
+  Twc.q[1] = q_xyzw[0];
+  Twc.q[2] = q_xyzw[1];
+  Twc.q[3] = q_xyzw[2];
+  for (int k = 0; k < 3; k++) Twc.t[k] = p[k];
+  normalize(Twc);
+  const Se3h Tcw = inverse(Twc);
+  for (int k = 0; k < 4; k++) T[k] = Tcw.q[k];
+  for (int k = 0; k < 3; k++) T[4 + k] = Tcw.t[k];
+  T[7] = 0;
+}
+inline void estimate_to_pose(const double* T, double* q_xyzw, double* p) {
+  Se3h Tcw;
+  for (int k = 0; k < 4; k++) Tcw.q[k] = T[k];
+  for (int k = 0; k < 3; k++) Tcw.t[k] = T[4 + k];
+  const Se3h Twc = inverse(Tcw);
+  q_xyzw[0] = Twc.q[1];
+  q_xyzw[1] = Twc.q[2];
+  q_xyzw[2] = Twc.q[3];
+  q_xyzw[3] = Twc.q[0];
+  for (int k = 0; k < 3; k++) p[k] = Twc.t[k];
+}
+
 }  // namespace se3h
 }  // namespace rspl
