@@ -1599,6 +1599,121 @@ int rspl_lmap_debug_global_plan(int max_keypoints, int max_local_points, int* ch
  * cap / *n protocol of rspl_map_local_mappoints. */
 int rspl_map_good_mappoints(const rspl_map* m, int32_t* ids, double* positions, int cap, int* n);
 
+
+/* ------------------------------------------------------------------------ */
+/* Loop closure: pose-graph optimisation over all keyframes on a tile-sparse */
+/* fp64 Cholesky.  The reference has no such stage;      */
+/* parity is with tests/pgo_ref.py.                                          */
+/*   poses     T_wc: pose_q x y z w (as rspl_ba_problem), pose_p             */
+/*   edge      measured Z = T_wi^-1 T_wj, weights (w_t, w_r);                */
+/*             d = R_i^T (p_j - p_i), e_t = d - t_Z,                         */
+/*             e_R = Log(R_Z^T R_i^T R_j) through the quaternion, w >= 0     */
+/*   cost      F = sum w_t |e_t|^2 + w_r |e_R|^2                             */
+/*   update    p <- p + dp, R <- R Exp(dphi) on the free poses               */
+/*   LM        H = sum J^T W J, b = -sum J^T W e, lambda_0 = 1e-5 max diag H;*/
+/*             a trial solves (H + lambda I) d = b by Cholesky;              */
+/*             rho = (F - F_new) / (d^T (lambda d + b)); rho > 0 and F_new   */
+/*             finite accepts: lambda *= max(1/3, 1 - (2 rho - 1)^3), nu = 2;*/
+/*             otherwise (a non-positive pivot included) lambda *= nu,       */
+/*             nu *= 2; ten rejections in a row end the call; a trial whose  */
+/*             predicted decrease d^T (lambda d + b) is at most 1e-12 F ends */
+/*             it converged, the step not applied: F carries rounding noise  */
+/*             of about 2 u |d| / |e| relative (1e-14 at metres of motion    */
+/*             and centimetres of residual), below which rho's sign, and     */
+/*             with it status and iteration count, would be noise            */
+/* Refused with RSPL_E_ARG: no fixed pose; an edge with i == j or an index   */
+/* out of range; a connected component with a free pose that has an edge but */
+/* no fixed pose.  A free pose without an edge comes back unchanged (where no */
+/* free pose has an edge: zero iterations, converged), an edge between fixed */
+/* poses only adds to the cost, duplicate edges sum.                         */
+/* ------------------------------------------------------------------------ */
+#define RSPL_PGO_CONVERGED 0      /* an accepted step with max |d| < step_tol, a trial the cost cannot resolve, or
+                                   * nothing to optimise */
+#define RSPL_PGO_MAX_ITERATIONS 1 /* max_iterations accepted steps */
+#define RSPL_PGO_STALLED 2        /* ten rejections in a row */
+
+typedef struct rspl_pgo rspl_pgo;
+typedef struct {
+  int max_poses; /* 1..4096 */
+  int max_edges;
+  int max_tiles; /* 96 x 96 fp64 tiles of the factor the handle can hold (73728 bytes each) */
+  int device;
+} rspl_pgo_config;
+
+typedef struct {
+  int n_poses;
+  const double* pose_q;      /* [n_poses][4] */
+  const double* pose_p;      /* [n_poses][3] */
+  const uint8_t* pose_fixed; /* [n_poses] */
+  int n_edges;
+  const int32_t* edge_i;     /* [n_edges] */
+  const int32_t* edge_j;
+  const double* edge_q;      /* [n_edges][4] */
+  const double* edge_p;      /* [n_edges][3] */
+  const double* edge_w;      /* [n_edges][2] (w_t, w_r) */
+} rspl_pgo_problem;
+
+typedef struct {
+  int max_iterations; /* 0: 30 */
+  double step_tol;    /* 0: 1e-10 */
+} rspl_pgo_params;
+
+typedef struct {
+  double* pose_q; /* caller arrays [n_poses][4], [n_poses][3] */
+  double* pose_p;
+  int status;     /* RSPL_PGO_* */
+  int iterations; /* accepted steps */
+  int trials;
+  int n_free;
+  int n_tiles;        /* lower-triangle tiles an edge or a free pose touches */
+  int n_filled_tiles; /* the same after the tile-level symbolic factorisation: what is stored and computed */
+  double cost_initial, cost_final, lambda;
+} rspl_pgo_result;
+
+/* A handle allocates everything at create.  Free poses keep the caller's order; tile t holds free poses
+ * 16 t .. 16 t + 15.  A problem beyond max_poses / max_edges, or whose plan needs more than max_tiles tiles, fails
+ * with RSPL_E_CAPACITY before any launch; a factorisation that never succeeds fails with RSPL_E_SOLVER.  LM control
+ * runs on the host with one synchronisation per trial.  The result repeats bit for bit from call to call. */
+int rspl_pgo_create(const rspl_pgo_config* cfg, rspl_pgo** out);
+void rspl_pgo_destroy(rspl_pgo* h);
+int rspl_pgo_solve(rspl_pgo* h, const rspl_pgo_problem* problem, const rspl_pgo_params* params,
+                   rspl_pgo_result* result);
+
+/* debug (parity tests): the host twin -- the text of csrc/pgo_solve.hpp, the same tile plan and LM rule on plain
+ * C++ tiles; no device is touched */
+int rspl_pgo_debug_host(const rspl_pgo_problem* problem, const rspl_pgo_params* params, rspl_pgo_result* result);
+/* debug: the tile plan of a problem, host only.  Each output may be NULL; tile_map [tiles_per_side][tiles_per_side]
+ * (map_cap >= tiles_per_side^2 entries, RSPL_E_CAPACITY otherwise) receives the storage index of each filled
+ * lower-triangle tile, -1 elsewhere. */
+int rspl_pgo_debug_plan(const rspl_pgo_problem* problem, int* n_free, int* tiles_per_side, int* n_tiles,
+                        int* n_filled_tiles, int32_t* tile_map, int map_cap);
+/* debug: one linearisation at the problem's poses and one solve of (H + lambda I) delta = b on the device.
+ * e [n_edges][6], b [6 n_free], delta [6 n_free], H_dense [6 n_free][6 n_free] (H without lambda; NULL is required
+ * when 6 n_free > 1536); each may be NULL.  RSPL_E_SOLVER for a non-positive pivot. */
+int rspl_pgo_debug_system(rspl_pgo* h, const rspl_pgo_problem* problem, double lambda, double* e, double* b,
+                          double* H_dense, double* delta);
+
+/* The pose graph of the native map.  Nodes: every keyframe in ascending id with its pose.  Edges: each keyframe's
+ * parent edge plus every connection of weight >= min_weight, each unordered pair once as (lower id, higher id) in
+ * ascending (i, j) order; edge_i / edge_j index the node list; Z = T_wi^-1 T_wj from the current poses;
+ * edge_weight is the connection weight, 0 for a parent-only pair.  *n_nodes and *n_edges are always set; the arrays
+ * (each may be NULL) are written when node_cap >= *n_nodes and edge_cap >= *n_edges, otherwise nothing is written
+ * and the call fails with RSPL_E_CAPACITY. */
+int rspl_map_pose_graph(const rspl_map* m, int min_weight, int32_t* frame_ids, double* pose_q, double* pose_p,
+                        int node_cap, int* n_nodes, int32_t* edge_i, int32_t* edge_j, double* edge_q, double* edge_p,
+                        int32_t* edge_weight, int edge_cap, int* n_edges);
+/* Set the poses of the listed keyframes (an unknown or repeated frame id is RSPL_E_ARG before the map changes).
+ * Every non-bad map point with a position and every map line moves rigidly with its anchor, X' = T' T^-1 X (a line's
+ * Pluecker coordinates and endpoints by the same motion); the anchor is its lowest-id observer among the listed
+ * frames, and a landmark no listed frame observes stays where it is. */
+int rspl_map_apply_pose_graph(rspl_map* m, int n, const int32_t* frame_ids, const double* pose_q,
+                              const double* pose_p);
+/* Loop candidates for keyframe frame_id: every observer of point_ids[n] (map point id or -1; bad and unknown ids
+ * are skipped) gets one vote per point; frame_id itself, its connections and the frames within min_gap frame ids
+ * of it are left out.  Descending votes, ties to the lower id; the cap / *n protocol of rspl_map_local_mappoints. */
+int rspl_map_loop_candidates(const rspl_map* m, int frame_id, int n, const int32_t* point_ids, int min_gap,
+                             int32_t* ids, int32_t* votes, int cap, int* n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,8 @@ _API = ("SuperPoint", "SuperPointConfig", "SuperGlue", "SuperGlueConfig", "Point
         "LocalmapOptimization", "LocalBA", "FrameOptimization", "FrameBA",
         "ShardGroup", "Comm", "comm_unique_id", "broadcast_comm_id", "PnP", "SolvePnPWithCV",
         "Tracker", "TrackFrame", "KeyframeBuilder", "triangulate_points", "stereo_window", "FundamentalRansac",
-        "LocalMap", "TrackLocalMap", "lmap_search_host", "lmap_global_host", "lmap_global_plan", "Relocalise")
+        "LocalMap", "TrackLocalMap", "lmap_search_host", "lmap_global_host", "lmap_global_plan", "Relocalise",
+        "PoseGraph", "pgo_host", "pgo_plan", "pgo_system", "CloseLoop")
 
 
 def __getattr__(name):

@@ -1313,6 +1313,163 @@ def TrackLocalMap(map_, local_map: LocalMap, tracker: "Tracker", frame: dict, re
     return n, out
 
 
+# ---- loop closure: pose-graph optimisation ---------------------------------------------------
+PGO_CONVERGED, PGO_MAX_ITERATIONS, PGO_STALLED = 0, 1, 2  # RSPL_PGO_*
+
+
+def _pgo_problem(pose_q, pose_p, pose_fixed, edge_i, edge_j, edge_q, edge_p, edge_w):
+    """(PgoProblem, the arrays it points into)"""
+    q = np.ascontiguousarray(pose_q, np.float64).reshape(-1, 4)
+    p = np.ascontiguousarray(pose_p, np.float64).reshape(-1, 3)
+    fx = np.ascontiguousarray(pose_fixed, np.uint8).reshape(-1)
+    ei = np.ascontiguousarray(edge_i, np.int32).reshape(-1)
+    ej = np.ascontiguousarray(edge_j, np.int32).reshape(-1)
+    eq = np.ascontiguousarray(edge_q, np.float64).reshape(-1, 4)
+    ep = np.ascontiguousarray(edge_p, np.float64).reshape(-1, 3)
+    ew = np.ascontiguousarray(edge_w, np.float64).reshape(-1, 2)
+    if not (len(q) == len(p) == len(fx)) or not (len(ei) == len(ej) == len(eq) == len(ep) == len(ew)):
+        raise ValueError("pose graph: array lengths differ")
+    keep = (q, p, fx, ei, ej, eq, ep, ew)
+    P = capi.PgoProblem(len(q), q.ctypes.data, p.ctypes.data, fx.ctypes.data, len(ei), ei.ctypes.data, ej.ctypes.data,
+                        eq.ctypes.data, ep.ctypes.data, ew.ctypes.data)
+    return P, keep
+
+
+def _pgo_run(fn, what, P, max_iterations, step_tol):
+    q, p = np.empty((P.n_poses, 4)), np.empty((P.n_poses, 3))
+    R = capi.PgoResult()
+    R.pose_q, R.pose_p = q.ctypes.data, p.ctypes.data
+    pr = capi.PgoParams(int(max_iterations), float(step_tol))
+    capi.check(fn(C.byref(P), C.byref(pr), C.byref(R)), what)
+    return dict(pose_q=q, pose_p=p, status=R.status, iterations=R.iterations, trials=R.trials, n_free=R.n_free,
+                n_tiles=R.n_tiles, n_filled_tiles=R.n_filled_tiles, cost_initial=R.cost_initial,
+                cost_final=R.cost_final, lam=R.lambda_)
+
+
+class PoseGraph:
+    """Owns one rspl_pgo handle: LM over a pose graph on a tile-sparse fp64 Cholesky (the loop-closure correction).
+    ``solve`` takes T_wc poses (q xyzw, p), a fixed mask and edges (i, j, Z = T_wi^-1 T_wj as q, p, weights (w_t, w_r))
+    and returns a dict: pose_q, pose_p, status (PGO_*), iterations, trials, both costs, lam and the plan's counts."""
+
+    def __init__(self, max_poses=1024, max_edges=8192, max_tiles=512, device=0):
+        self._lib = capi.load()
+        self._h = C.c_void_p()
+        self.max_poses, self.max_edges, self.max_tiles = int(max_poses), int(max_edges), int(max_tiles)
+        cfg = capi.PgoConfig(self.max_poses, self.max_edges, self.max_tiles, int(device))
+        capi.check(self._lib.rspl_pgo_create(C.byref(cfg), C.byref(self._h)), "rspl_pgo_create")
+
+    def solve(self, pose_q, pose_p, pose_fixed, edge_i, edge_j, edge_q, edge_p, edge_w, max_iterations=0, step_tol=0.0):
+        P, keep = _pgo_problem(pose_q, pose_p, pose_fixed, edge_i, edge_j, edge_q, edge_p, edge_w)
+        return _pgo_run(lambda *a: self._lib.rspl_pgo_solve(self._h, *a), "rspl_pgo_solve", P, max_iterations, step_tol)
+
+    def system(self, pose_q, pose_p, pose_fixed, edge_i, edge_j, edge_q, edge_p, edge_w, lam, dense=True):
+        """rspl_pgo_debug_system: (e [E][6], b, H dense or None, delta) of one linearisation and one solve at lam"""
+        P, keep = _pgo_problem(pose_q, pose_p, pose_fixed, edge_i, edge_j, edge_q, edge_p, edge_w)
+        n = 6 * int((keep[2] == 0).sum())
+        e, b, d = np.zeros((P.n_edges, 6)), np.zeros(n), np.zeros(n)
+        H = np.zeros((n, n)) if dense else None
+        capi.check(self._lib.rspl_pgo_debug_system(self._h, C.byref(P), float(lam), e.ctypes.data, b.ctypes.data,
+                                                   H.ctypes.data if dense else None, d.ctypes.data),
+                   "rspl_pgo_debug_system")
+        return e, b, H, d
+
+    def close(self):
+        if self._h:
+            self._lib.rspl_pgo_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+
+def pgo_system(pose_graph: PoseGraph, *problem, lam, dense=True):
+    """rspl_pgo_debug_system on a PoseGraph handle (see PoseGraph.system)"""
+    return pose_graph.system(*problem, lam=lam, dense=dense)
+
+
+def pgo_host(pose_q, pose_p, pose_fixed, edge_i, edge_j, edge_q, edge_p, edge_w, max_iterations=0, step_tol=0.0):
+    """rspl_pgo_debug_host: the solver's host twin (same arithmetic text, tile plan and LM rule); no device"""
+    P, keep = _pgo_problem(pose_q, pose_p, pose_fixed, edge_i, edge_j, edge_q, edge_p, edge_w)
+    return _pgo_run(capi.load().rspl_pgo_debug_host, "rspl_pgo_debug_host", P, max_iterations, step_tol)
+
+
+def pgo_plan(pose_fixed, edge_i, edge_j, tile_map=False):
+    """rspl_pgo_debug_plan: dict n_free, tiles_per_side, n_tiles, n_filled_tiles (and tile_map [nt][nt])"""
+    n = len(pose_fixed)
+    q = np.tile(np.array([0.0, 0.0, 0.0, 1.0]), (n, 1))
+    ne = len(edge_i)
+    P, keep = _pgo_problem(q, np.zeros((n, 3)), pose_fixed, edge_i, edge_j, np.tile(q[:1], (ne, 1)), np.zeros((ne, 3)),
+                           np.ones((ne, 2)))
+    nf, nt, ns, nfl = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    lib = capi.load()
+    capi.check(lib.rspl_pgo_debug_plan(C.byref(P), C.byref(nf), C.byref(nt), C.byref(ns), C.byref(nfl), None, 0),
+               "rspl_pgo_debug_plan")
+    out = dict(n_free=nf.value, tiles_per_side=nt.value, n_tiles=ns.value, n_filled_tiles=nfl.value)
+    if tile_map:
+        tm = np.empty((nt.value, nt.value), np.int32)
+        capi.check(lib.rspl_pgo_debug_plan(C.byref(P), None, None, None, None, tm.ctypes.data, tm.size),
+                   "rspl_pgo_debug_plan")
+        out["tile_map"] = tm
+    return out
+
+
+def _rt_to_qp(R, t):
+    """a rotation matrix and a translation as (q xyzw, p)"""
+    from .trajectory import quat_from_R
+    q = quat_from_R(np.asarray(R, np.float64))
+    return q / np.linalg.norm(q), np.asarray(t, np.float64).copy()
+
+
+def CloseLoop(map_, local_map: LocalMap, pnp: "PnP", pose_graph: PoseGraph, frame: dict, keyframe_id: int,
+              min_votes=20, min_inliers=30, min_gap=10, min_weight=1, stream=None):
+    """Loop closure for keyframe ``keyframe_id``, whose features are ``frame`` (``d_features``, ``d_n1``, ``cam``):
+
+    1. the global descriptor search of the frame over ``map_.GoodMappoints()``; 2. ``map_.LoopCandidates`` on the
+    matched ids -- a best candidate below ``min_votes``: (False, info), stage "vote"; 3. ``pnp.solve`` (100
+    iterations, 20 px, 0.99, as ``Relocalise``) on the matches whose point the candidate or one of its connections
+    observes -- fewer than ``min_inliers`` inliers: (False, info), stage "pnp"; 4. ``map_.PoseGraph(min_weight)`` plus
+    one loop edge from the candidate to the keyframe with Z = T_cand^-1 T_pnp, all weights 1, the lowest-id keyframe
+    fixed; 5. ``pose_graph.solve``, then ``map_.ApplyPoseGraph``.  Returns (True, info) with ``cost_initial``,
+    ``cost_final``, ``iterations``, ``status``, ``candidate``, ``votes``, ``pnp_inliers``.  Tracker slots and the
+    local table hold the old poses and positions afterwards: refresh them."""
+    ids, pos = map_.GoodMappoints()
+    local_map.set_local(ids, pos, stream)
+    local_map.global_enqueue([frame], stream=stream)
+    g = local_map.global_fetch()[0]
+    nm = g["n_matched"]
+    mid = np.asarray(g["match_id"][:nm], np.int32)
+    cand, votes = map_.LoopCandidates(keyframe_id, mid, min_gap)
+    info = dict(stage="vote", n_matched=nm, candidate=int(cand[0]) if len(cand) else -1,
+                votes=int(votes[0]) if len(votes) else 0)
+    if len(cand) == 0 or votes[0] < min_votes:
+        return False, info
+    c = int(cand[0])
+    near = {c} | {f for _, f in map_.GetOrderedConnections(c)}
+    keep = np.array([k for k in range(nm) if near & set(map_.GetMappoint(int(mid[k]))[2])], np.int64)
+    cam = frame["cam"]
+    k, Rwc, twc, inl, _ = pnp.solve([(tuple(cam[:4]), g["match_pos"][:nm][keep], g["match_xy"][:nm][keep])], 100, 20.0,
+                                    0.99)[0]
+    info.update(stage="pnp", n_near=len(keep), pnp_inliers=k)
+    if k < min_inliers:
+        return False, info
+    G = map_.PoseGraph(min_weight)
+    fid = G["frame_ids"]
+    ic, ik = int(np.searchsorted(fid, c)), int(np.searchsorted(fid, keyframe_id))
+    Tc = map_.GetPose(c)
+    Rz = Tc[:3, :3].T @ np.asarray(Rwc).reshape(3, 3)
+    lq, lp = _rt_to_qp(Rz, Tc[:3, :3].T @ (np.asarray(twc, np.float64) - Tc[:3, 3]))
+    fixed = np.zeros(len(fid), np.uint8)
+    fixed[0] = 1
+    E = len(G["edge_i"]) + 1
+    out = pose_graph.solve(G["pose_q"], G["pose_p"], fixed, np.append(G["edge_i"], ic), np.append(G["edge_j"], ik),
+                           np.vstack([G["edge_q"], lq]), np.vstack([G["edge_p"], lp]), np.ones((E, 2)))
+    map_.ApplyPoseGraph(fid, out["pose_q"], out["pose_p"])
+    info.update(stage="done", cost_initial=out["cost_initial"], cost_final=out["cost_final"],
+                iterations=out["iterations"], status=out["status"], pnp_Rwc=np.asarray(Rwc).reshape(3, 3),
+                pnp_twc=np.asarray(twc, np.float64))
+    return True, info
+
+
 from .synthetic import stereo_window  # noqa: E402  (Camera's disparity window from bf and the depth thresholds)
 
 KF_NEW_NONE, KF_NEW_GOOD, KF_NEW_UNTRIANGULATED = 0, 1, 2  # RSPL_KF_NEW_*

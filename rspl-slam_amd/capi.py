@@ -71,6 +71,8 @@ EXPORTS = [
     "rspl_lmap_debug_search_host", "rspl_map_reference_keyframe", "rspl_map_local_mappoints",
     "rspl_lmap_global_enqueue", "rspl_lmap_global_fetch", "rspl_lmap_debug_global_host", "rspl_lmap_debug_global_plan",
     "rspl_map_good_mappoints",
+    "rspl_pgo_create", "rspl_pgo_destroy", "rspl_pgo_solve", "rspl_pgo_debug_host", "rspl_pgo_debug_plan",
+    "rspl_pgo_debug_system", "rspl_map_pose_graph", "rspl_map_apply_pose_graph", "rspl_map_loop_candidates",
 ]
 
 
@@ -277,6 +279,26 @@ class LmapGlobalHostProblem(C.Structure):
                 ("local_pos", C.c_void_p), ("local_desc", C.c_void_p)]
 
 
+class PgoConfig(C.Structure):
+    _fields_ = [("max_poses", C.c_int), ("max_edges", C.c_int), ("max_tiles", C.c_int), ("device", C.c_int)]
+
+
+class PgoProblem(C.Structure):
+    _fields_ = [("n_poses", C.c_int), ("pose_q", C.c_void_p), ("pose_p", C.c_void_p), ("pose_fixed", C.c_void_p),
+                ("n_edges", C.c_int), ("edge_i", C.c_void_p), ("edge_j", C.c_void_p), ("edge_q", C.c_void_p),
+                ("edge_p", C.c_void_p), ("edge_w", C.c_void_p)]
+
+
+class PgoParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int), ("step_tol", C.c_double)]
+
+
+class PgoResult(C.Structure):
+    _fields_ = [("pose_q", C.c_void_p), ("pose_p", C.c_void_p), ("status", C.c_int), ("iterations", C.c_int),
+                ("trials", C.c_int), ("n_free", C.c_int), ("n_tiles", C.c_int), ("n_filled_tiles", C.c_int),
+                ("cost_initial", C.c_double), ("cost_final", C.c_double), ("lambda_", C.c_double)]
+
+
 class RsplError(RuntimeError):
     pass
 
@@ -472,6 +494,19 @@ def load(path: pathlib.Path = LIB_PATH):
                                                     C.POINTER(LmapGlobalResult)]
         lib.rspl_lmap_debug_global_plan.argtypes = [ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
         lib.rspl_map_good_mappoints.argtypes = [vp, vp, vp, ip, C.POINTER(ip)]
+    if hasattr(lib, "rspl_pgo_create"):
+        lib.rspl_pgo_create.argtypes = [C.POINTER(PgoConfig), C.POINTER(vp)]
+        lib.rspl_pgo_destroy.argtypes = [vp]
+        lib.rspl_pgo_destroy.restype = None
+        lib.rspl_pgo_solve.argtypes = [vp, C.POINTER(PgoProblem), C.POINTER(PgoParams), C.POINTER(PgoResult)]
+        lib.rspl_pgo_debug_host.argtypes = [C.POINTER(PgoProblem), C.POINTER(PgoParams), C.POINTER(PgoResult)]
+        lib.rspl_pgo_debug_plan.argtypes = [C.POINTER(PgoProblem), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip),
+                                            C.POINTER(ip), vp, ip]
+        lib.rspl_pgo_debug_system.argtypes = [vp, C.POINTER(PgoProblem), dp, vp, vp, vp, vp]
+        lib.rspl_map_pose_graph.argtypes = [vp, ip, vp, vp, vp, ip, C.POINTER(ip), vp, vp, vp, vp, vp, ip,
+                                            C.POINTER(ip)]
+        lib.rspl_map_apply_pose_graph.argtypes = [vp, ip, vp, vp, vp]
+        lib.rspl_map_loop_candidates.argtypes = [vp, ip, ip, vp, ip, vp, vp, ip, C.POINTER(ip)]
     _lib = lib
     return lib
 

@@ -1560,3 +1560,172 @@ extern "C" int rspl_map_good_mappoints(const rspl_map* m, int32_t* ids, double* 
   }
   return RSPL_OK;
 }
+
+// ---- loop closure: the pose graph out, the corrected poses back in, the candidate vote ------
+// The reference has no such stage.  All three are host walks of the native map.
+extern "C" int rspl_map_pose_graph(const rspl_map* m, int min_weight, int32_t* frame_ids, double* pose_q, double* pose_p,
+                                   int node_cap, int* n_nodes, int32_t* edge_i, int32_t* edge_j, double* edge_q,
+                                   double* edge_p, int32_t* edge_weight, int edge_cap, int* n_edges) {
+  RSPL_CHECK_ARG(m && n_nodes && n_edges && node_cap >= 0 && edge_cap >= 0, "rspl_map_pose_graph: bad argument");
+  const std::vector<int>& ids = m->kf_sorted;
+  std::map<std::pair<int, int>, int> pairs;  // (lower id, higher id) -> connection weight, 0: parent only
+  for (int id : ids) {
+    const MFrame& f = m->kf.at(id);
+    if (f.parent >= 0 && f.parent != id && m->kf.count(f.parent))
+      pairs.insert({{std::min(id, f.parent), std::max(id, f.parent)}, 0});
+  }
+  for (int id : ids)
+    for (auto& kv : m->kf.at(id).conn) {
+      if (kv.second < min_weight || kv.first == id || !m->kf.count(kv.first)) continue;
+      int& w = pairs[{std::min(id, kv.first), std::max(id, kv.first)}];
+      w = std::max(w, kv.second);
+    }
+  *n_nodes = (int)ids.size();
+  *n_edges = (int)pairs.size();
+  if (node_cap < *n_nodes || edge_cap < *n_edges) {
+    set_error("rspl_map_pose_graph: capacities %d, %d < %d keyframes, %d edges", node_cap, edge_cap, *n_nodes, *n_edges);
+    return RSPL_E_CAPACITY;
+  }
+  for (size_t i = 0; i < ids.size(); i++) {
+    const MFrame& f = m->kf.at(ids[i]);
+    if (frame_ids) frame_ids[i] = ids[i];
+    if (pose_q) {
+      R_to_q(f.Twc, 4, pose_q + 4 * i);
+      const double* q = pose_q + 4 * i;
+      const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+      for (int c = 0; c < 4; c++) pose_q[4 * i + c] /= nq;
+    }
+    if (pose_p)
+      for (int c = 0; c < 3; c++) pose_p[3 * i + c] = f.Twc[4 * c + 3];
+  }
+  size_t e = 0;
+  for (auto& kv : pairs) {
+    const MFrame& a = m->kf.at(kv.first.first);
+    const MFrame& b = m->kf.at(kv.first.second);
+    if (edge_i) edge_i[e] = (int32_t)(std::lower_bound(ids.begin(), ids.end(), a.id) - ids.begin());
+    if (edge_j) edge_j[e] = (int32_t)(std::lower_bound(ids.begin(), ids.end(), b.id) - ids.begin());
+    double Rz[9], tz[3];  // Z = T_wa^-1 T_wb
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++)
+        Rz[3 * r + c] = a.Twc[r] * b.Twc[c] + a.Twc[4 + r] * b.Twc[4 + c] + a.Twc[8 + r] * b.Twc[8 + c];
+      tz[r] = a.Twc[r] * (b.Twc[3] - a.Twc[3]) + a.Twc[4 + r] * (b.Twc[7] - a.Twc[7]) + a.Twc[8 + r] * (b.Twc[11] - a.Twc[11]);
+    }
+    if (edge_q) {
+      double q[4];
+      R_to_q(Rz, 3, q);
+      const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+      for (int c = 0; c < 4; c++) edge_q[4 * e + c] = q[c] / nq;
+    }
+    if (edge_p) memcpy(edge_p + 3 * e, tz, sizeof(tz));
+    if (edge_weight) edge_weight[e] = kv.second;
+    e++;
+  }
+  return RSPL_OK;
+}
+
+extern "C" int rspl_map_apply_pose_graph(rspl_map* m, int n, const int32_t* frame_ids, const double* pose_q,
+                                         const double* pose_p) {
+  RSPL_CHECK_ARG(m && n >= 0 && (n == 0 || (frame_ids && pose_q && pose_p)), "rspl_map_apply_pose_graph: bad argument");
+  struct Motion {
+    double R[9], t[3];  // T' T^-1
+  };
+  std::map<int, Motion> motion;
+  for (int i = 0; i < n; i++) {
+    auto it = m->kf.find(frame_ids[i]);
+    RSPL_CHECK_ARG(it != m->kf.end(), "rspl_map_apply_pose_graph: unknown frame %d", frame_ids[i]);
+    RSPL_CHECK_ARG(!motion.count(frame_ids[i]), "rspl_map_apply_pose_graph: frame %d listed twice", frame_ids[i]);
+    const double* q = pose_q + 4 * (size_t)i;
+    const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    bool finite = std::isfinite(nq) && nq > 0;
+    for (int c = 0; c < 3; c++) finite = finite && std::isfinite(pose_p[3 * (size_t)i + c]);
+    RSPL_CHECK_ARG(finite, "rspl_map_apply_pose_graph: frame %d: bad pose", frame_ids[i]);
+    motion[frame_ids[i]] = Motion{};
+  }
+  for (int i = 0; i < n; i++) {
+    MFrame& f = m->kf.at(frame_ids[i]);
+    const double* q = pose_q + 4 * (size_t)i;
+    const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double qn[4] = {q[0] / nq, q[1] / nq, q[2] / nq, q[3] / nq};
+    double Rn[9];
+    q_to_R(qn, Rn, 3);
+    Motion& M = motion[frame_ids[i]];
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++)
+        M.R[3 * r + c] = Rn[3 * r] * f.Twc[4 * c] + Rn[3 * r + 1] * f.Twc[4 * c + 1] + Rn[3 * r + 2] * f.Twc[4 * c + 2];
+    for (int r = 0; r < 3; r++)
+      M.t[r] = pose_p[3 * (size_t)i + r] - (M.R[3 * r] * f.Twc[3] + M.R[3 * r + 1] * f.Twc[7] + M.R[3 * r + 2] * f.Twc[11]);
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) f.Twc[4 * r + c] = Rn[3 * r + c];
+      f.Twc[4 * r + 3] = pose_p[3 * (size_t)i + r];
+    }
+  }
+  auto anchor = [&](const FlatMap<int>& obs) -> const Motion* {
+    for (auto& kv : obs) {  // ascending frame id
+      if (kv.second < 0) continue;
+      auto it = motion.find(kv.first);
+      if (it != motion.end()) return &it->second;
+    }
+    return nullptr;
+  };
+  auto move = [](const Motion& M, const double* x, double* o) {
+    const double v[3] = {x[0], x[1], x[2]};
+    for (int r = 0; r < 3; r++) o[r] = M.R[3 * r] * v[0] + M.R[3 * r + 1] * v[1] + M.R[3 * r + 2] * v[2] + M.t[r];
+  };
+  for (auto& kv : m->mp) {
+    MPoint& p = kv.second;
+    if (p.type != kGood) continue;  // bad, or no position yet
+    if (const Motion* M = anchor(p.obs)) move(*M, p.p, p.p);
+  }
+  for (auto& kv : m->ml) {
+    MLine& l = kv.second;
+    if (l.type == kBad) continue;
+    const Motion* M = anchor(l.obs);
+    if (!M) continue;
+    // Pluecker (w, d): d' = R d, w' = R w + t x d'
+    double w[3], d[3];
+    for (int r = 0; r < 3; r++) {
+      w[r] = M->R[3 * r] * l.L[0] + M->R[3 * r + 1] * l.L[1] + M->R[3 * r + 2] * l.L[2];
+      d[r] = M->R[3 * r] * l.L[3] + M->R[3 * r + 1] * l.L[4] + M->R[3 * r + 2] * l.L[5];
+    }
+    l.L[0] = w[0] + M->t[1] * d[2] - M->t[2] * d[1];
+    l.L[1] = w[1] + M->t[2] * d[0] - M->t[0] * d[2];
+    l.L[2] = w[2] + M->t[0] * d[1] - M->t[1] * d[0];
+    for (int r = 0; r < 3; r++) l.L[3 + r] = d[r];
+    if (l.ep_valid) {
+      move(*M, l.ep, l.ep);
+      move(*M, l.ep + 3, l.ep + 3);
+    }
+  }
+  return RSPL_OK;
+}
+
+extern "C" int rspl_map_loop_candidates(const rspl_map* m, int frame_id, int n, const int32_t* point_ids, int min_gap,
+                                        int32_t* ids, int32_t* votes, int cap, int* n_out) {
+  RSPL_CHECK_ARG(m && n_out && (n == 0 || point_ids) && n >= 0 && cap >= 0, "rspl_map_loop_candidates: bad argument");
+  auto fit = m->kf.find(frame_id);
+  RSPL_CHECK_ARG(fit != m->kf.end(), "rspl_map_loop_candidates: unknown frame %d", frame_id);
+  std::map<int, int> count;
+  for (int i = 0; i < n; i++) {
+    auto it = point_ids[i] < 0 ? m->mp.end() : m->mp.find(point_ids[i]);
+    if (it == m->mp.end() || it->second.type == kBad) continue;
+    for (auto& kv : it->second.obs) {
+      const int f = kv.first;
+      if (kv.second < 0 || f == frame_id || !m->kf.count(f) || fit->second.conn.count(f)) continue;  // < 0: removed
+      if (std::abs((long)f - (long)frame_id) <= (long)min_gap) continue;
+      count[f]++;
+    }
+  }
+  std::vector<std::pair<int, int>> order(count.begin(), count.end());  // ascending id
+  std::stable_sort(order.begin(), order.end(),
+                   [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.second > b.second; });
+  *n_out = (int)order.size();
+  if (cap < *n_out) {
+    set_error("rspl_map_loop_candidates: capacity %d < %d candidates", cap, *n_out);
+    return RSPL_E_CAPACITY;
+  }
+  for (size_t i = 0; i < order.size(); i++) {
+    if (ids) ids[i] = order[i].first;
+    if (votes) votes[i] = order[i].second;
+  }
+  return RSPL_OK;
+}

@@ -274,6 +274,50 @@ class Map:
                    "rspl_map_good_mappoints")
         return ids[:n.value].copy(), pos[:n.value].copy()
 
+    # ---- loop closure (the reference has no such stage) ----
+    def PoseGraph(self, min_weight: int = 1) -> dict:
+        """Every keyframe in ascending id with its pose, and one edge per unordered pair that is a parent edge or a
+        connection of weight >= ``min_weight``, as (lower id, higher id) in ascending order, Z = T_wi^-1 T_wj from the
+        current poses: dict frame_ids, pose_q, pose_p, edge_i, edge_j (indices into frame_ids), edge_q, edge_p,
+        edge_weight (0: parent only)."""
+        nn, ne = C.c_int(), C.c_int()
+        self._lib.rspl_map_pose_graph(self._h, int(min_weight), None, None, None, 0, C.byref(nn), None, None, None,
+                                      None, None, 0, C.byref(ne))  # the counts
+        N, E = nn.value, ne.value
+        ids, q, p = np.zeros(N, np.int32), np.zeros((N, 4)), np.zeros((N, 3))
+        ei, ej, ew = np.zeros(E, np.int32), np.zeros(E, np.int32), np.zeros(E, np.int32)
+        eq, ep = np.zeros((E, 4)), np.zeros((E, 3))
+        capi.check(self._lib.rspl_map_pose_graph(self._h, int(min_weight), ids.ctypes.data, q.ctypes.data,
+                                                 p.ctypes.data, N, C.byref(nn), ei.ctypes.data, ej.ctypes.data,
+                                                 eq.ctypes.data, ep.ctypes.data, ew.ctypes.data, E, C.byref(ne)),
+                   "rspl_map_pose_graph")
+        return dict(frame_ids=ids, pose_q=q, pose_p=p, edge_i=ei, edge_j=ej, edge_q=eq, edge_p=ep, edge_weight=ew)
+
+    def ApplyPoseGraph(self, frame_ids, pose_q, pose_p):
+        """Set those keyframes' poses; every map point with a position and every map line moves rigidly with its
+        lowest-id observer among them (X' = T' T^-1 X); a landmark none of them observes stays."""
+        ids = np.ascontiguousarray(frame_ids, np.int32)
+        q = np.ascontiguousarray(pose_q, np.float64).reshape(-1, 4)
+        p = np.ascontiguousarray(pose_p, np.float64).reshape(-1, 3)
+        if not len(ids) == len(q) == len(p):
+            raise ValueError("ApplyPoseGraph: array lengths differ")
+        capi.check(self._lib.rspl_map_apply_pose_graph(self._h, len(ids), ids.ctypes.data, q.ctypes.data,
+                                                       p.ctypes.data), "rspl_map_apply_pose_graph")
+
+    def LoopCandidates(self, frame_id: int, point_ids, min_gap: int = 10):
+        """One vote per point for every observer of ``point_ids`` (id or -1), ``frame_id``, its connections and the
+        frames within ``min_gap`` ids of it aside: (frame ids, votes) by descending votes, ties to the lower id."""
+        a = np.ascontiguousarray(point_ids, np.int32)
+        n = C.c_int()
+        self._lib.rspl_map_loop_candidates(self._h, frame_id, len(a), a.ctypes.data, int(min_gap), None, None, 0,
+                                           C.byref(n))  # the count (or a refusal, reported below)
+        cap = n.value
+        ids, votes = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        capi.check(self._lib.rspl_map_loop_candidates(self._h, frame_id, len(a), a.ctypes.data, int(min_gap),
+                                                      ids.ctypes.data, votes.ctypes.data, cap, C.byref(n)),
+                   "rspl_map_loop_candidates")
+        return ids[:n.value].copy(), votes[:n.value].copy()
+
     # ---- Map::LocalMapOptimization ----
     def LocalMapOptimization(self, frame_id: int, ba) -> dict:
         """The whole of Map::LocalMapOptimization(new_frame) with the GPU local BA of `ba` (LocalBA)."""
